@@ -7,6 +7,25 @@ slab-decomposed over N MI355X GPUs (one process per GPU, device-resident halo ex
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run (no --full) does only what the headline figure needs: it builds the engine in its
+default configuration (z slabs, the transport's default schedule, hipGraph replay in one process and
+eager launches across processes), runs W warm-up steps and, on a GPU, untimed settling passes of K
+steps each until at least 100 steps have run ("settle_steps" in the JSON: the device's first steps
+on a fresh grid are 2 - 4 % slower than its steady state, which the median repetition of --full
+reports), times exactly K steps once, writes its outputs if --dump-outputs is given and prints the
+JSON line. Everything else described below (the N > 1 correctness gate, the timed trials that pick
+transport / graph mode / rounds / overlap / pencils, the three timed repetitions, the verification
+of the timed run against the naive kernels, the N > 1 diagnostic pass and the measured copy
+yardstick) runs only with --full; the JSON fields they fill are null without it.
+
+--dump-outputs DIR writes, after the timed steps, the field the timed engine holds after its last
+timed step (step W + settle_steps + K of a plain run) as DIR/field.npy (float32; float64 for
+--dtype f64): the whole grid (nz, ny, nx) in C order when it has at most 4 Mi cells, else its values
+at 4 Mi cell indices drawn once from a fixed seed (numpy default_rng(1).integers(0, cells, 4 Mi),
+sorted; flat index = (z * ny + y) * nx + x), so two builds run with the same arguments write
+comparable arrays. With --residual-every the last
+residual is written as DIR/residual.npy (float64).
+
 Launch. Under a launcher (RANK / WORLD_SIZE set) this process is one rank and WORLD_SIZE must equal
 --gpus. Without one, --gpus N > 1 spawns N child processes of this script with the launcher
 variables set (before this process touches the GPU) and exits with the worst child status; N
@@ -30,7 +49,7 @@ identical to five single steps, tests/test_gpu_temporal.py): every step is still
 the fused kernel keeps u^{t+1}..u^{t+4} on chip. A step count that is not a multiple of 5 ends with
 a shorter fused sweep.
 --temporal 1 measures one sweep per step. Timing: W untimed warmup steps, then exactly K steps bracketed by barrier +
-torch.cuda.synchronize() on both sides; the slowest rank's time is reported (N > 1: three such
+torch.cuda.synchronize() on both sides; the slowest rank's time is reported (--full: three such
 repetitions by default, the median reported and all three listed). GCells/s = nx*ny*nz*K / t / 1e9
 for the whole job.
 
@@ -92,10 +111,12 @@ def parse(argv=None):
     p.add_argument("--virtual-ranks", type=int, default=0,
                    help="split the grid into P slabs inside ONE process (loopback transport)")
     p.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
-                   help="replay 2-sweep cycles as hipGraphs; auto = gate and time both, keep the faster")
+                   help="replay 2-sweep cycles as hipGraphs; auto = on in one process and off across processes, "
+                        "with --full gate and time both and keep the faster")
     p.add_argument("--rounds", default="auto", choices=["auto", "1", "2"],
-                   help="minimum rounds of resident blocks per fused sweep; auto = 1 on one GPU, timed "
-                        "trial of 1 and 2 with several ranks (2 leaves CUs for exchange kernels mid-sweep)")
+                   help="minimum rounds of resident blocks per fused sweep; auto = the engine's default (1 on one "
+                        "GPU), with --full a timed trial of 1 and 2 with several ranks (2 leaves CUs for exchange "
+                        "kernels mid-sweep)")
     p.add_argument("--trial-steps", type=int, default=48,
                    help="steps of each short timed trial that picks transport / graph mode / rounds / "
                         "overlap (auto); every candidate is timed twice, interleaved, and its faster run counts")
@@ -111,13 +132,20 @@ def parse(argv=None):
                    help="only the overlapped schedule (interior || boundary + exchange; no trial)")
     p.add_argument("--residual-every", type=int, default=0)
     p.add_argument("--py", type=int, default=0,
-                   help="ranks along y of a (z, y) pencil decomposition (1 = z slabs; 0 = auto: at 4+ GPUs the "
-                        "3D 7-point tries slabs and 2-along-y pencils on the ipc transports and times the faster)")
+                   help="ranks along y of a (z, y) pencil decomposition (1 = z slabs; 0 = auto: z slabs, with --full "
+                        "at 4+ GPUs the 3D 7-point tries slabs and 2-along-y pencils and times the faster)")
     p.add_argument("--variant", default="auto", choices=["auto", "tuned", "naive"])
     p.add_argument("--device", default="auto", choices=["auto", "hip", "cpu"])
-    p.add_argument("--repeats", type=int, default=3,
+    p.add_argument("--repeats", type=int, default=0,
                    help="timed repetitions of --steps steps each, back to back; the median is reported and "
-                        "every one is listed")
+                        "every one is listed (0 = auto: 1, or 3 with --full or --rank-proxy)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: the N > 1 correctness gate, the timed "
+                        "trials of transport / graph mode / rounds / overlap / pencils, three timed repetitions, "
+                        "the verification of the timed run, the N > 1 diagnostic pass and the copy yardstick")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write the field of the last timed step (a fixed seeded sample of "
+                        "a large grid) as DIR/field.npy")
     p.add_argument("--trial-budget", type=float, default=150.0,
                    help="seconds the gate + trial phase may take before the second (interleaved) trial pass "
                         "is skipped (all ranks agree on the slowest rank's clock)")
@@ -141,7 +169,10 @@ def parse(argv=None):
                    help="allow more ranks than GPUs (processes share devices; tests of the ipc/staged paths "
                         "only: the ipc exchange's device spin waits assume one engine process per GPU and the "
                         "transport refuses shared GPUs without this)")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.repeats <= 0:
+        a.repeats = 3 if (a.full or a.rank_proxy > 0) else 1
+    return a
 
 
 _T0 = time.time()
@@ -500,6 +531,52 @@ def measure_copy_tbps(field_bytes):
     return 2.0 * n * 16 / best / 1e12
 
 
+# a GPU's first steps on a fresh grid run 2 - 4 % slower than the steady state it reaches within
+# about a hundred steps (1024^3 fp32: the repetitions of --full fall from 0.415 to 0.395 ms per step)
+SETTLE_MIN_STEPS = 100
+DUMP_MAX_CELLS = 4 << 20  # cells written by --dump-outputs (16 MiB of fp32, 32 MiB of fp64)
+DUMP_SEED = 1
+
+
+def dump_outputs(a, sim, prob, env, world, rank):
+    """--dump-outputs: the field after the last timed step as <dir>/field.npy on rank 0 (the whole
+    grid up to DUMP_MAX_CELLS cells, else its values at a fixed seeded sample of cell indices), and
+    the last residual as <dir>/residual.npy when one was evaluated. Every rank reads its own owned
+    cells from its current buffer; nothing is recomputed."""
+    import numpy as np
+    import torch.distributed as dist
+
+    nx, ny, nz = prob.nx, prob.ny, prob.nz
+    cells = nx * ny * nz
+    if cells <= DUMP_MAX_CELLS:
+        idx, shape = np.arange(cells, dtype=np.int64), (nz, ny, nx)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, cells, DUMP_MAX_CELLS, dtype=np.int64))
+        shape = (DUMP_MAX_CELLS,)
+    z, y, x = idx // (ny * nx), (idx // nx) % ny, idx % nx
+    sim.synchronize()
+    pieces = []
+    for i in range(sim.num_local):
+        lay = sim.layout(i)
+        own = _owned(sim, i, nx)
+        sel = np.nonzero((z >= lay["z0"]) & (z < lay["z1"]) & (y >= lay["y0"]) & (y < lay["y1"]))[0]
+        at = [torch.as_tensor(c[sel] - o, device=own.device) for c, o in ((z, lay["z0"]), (y, lay["y0"]), (x, 0))]
+        pieces.append((sel, own[at[0], at[1], at[2]].cpu().numpy()))
+    if env:
+        allp = [None] * world
+        dist.all_gather_object(allp, pieces)
+        pieces = [p for ps in allp for p in ps]
+    if rank != 0:
+        return
+    out = np.full(len(idx), np.nan, dtype=np.float64 if a.dtype == "f64" else np.float32)
+    for sel, vals in pieces:
+        out[sel] = vals
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    np.save(os.path.join(a.dump_outputs, "field.npy"), out.reshape(shape))
+    if sim.residual >= 0 and a.residual_every > 0:
+        np.save(os.path.join(a.dump_outputs, "residual.npy"), np.array([sim.residual], dtype=np.float64))
+
+
 def run_proxy(a):
     """--rank-proxy N: time exactly one rank's per-step work of an N-GPU strong-scaling run on one
     GPU (its slab plus K ghost planes per side, both boundary regions on the halo stream, the
@@ -509,6 +586,9 @@ def run_proxy(a):
 
     if not torch.cuda.is_available():
         print("bench: --rank-proxy needs a HIP device", file=sys.stderr)
+        return 2
+    if a.dump_outputs:
+        print("bench: --dump-outputs is not available with --rank-proxy", file=sys.stderr)
         return 2
     n = a.rank_proxy
     r = a.proxy_rank if a.proxy_rank >= 0 else (n // 2 if n > 1 else 0)
@@ -656,10 +736,11 @@ def main(argv=None):
     prob = make_problem(a, nx, ny, nz)
     # (z, y) pencils: py ranks along y. Auto: at 4+ processes the 3D 7-point (whose fused sweep
     # takes y ghost rows) tries 2 along y next to the z slabs, on every transport
+    full = a.full  # gate, trials, verification, diagnostics, copy yardstick (a plain run: none of them)
     if a.py > 0:
         pys = [a.py]
     else:
-        pys = [1, 2] if (env and world >= 4 and world % 2 == 0 and a.stencil == "heat7") else [1]
+        pys = [1, 2] if (full and env and world >= 4 and world % 2 == 0 and a.stencil == "heat7") else [1]
     temporal = pick_temporal(a, prob, max(1, world, a.virtual_ranks) // max(pys), hip)
     timeout = a.timeout if hip else 0.0
 
@@ -672,7 +753,7 @@ def main(argv=None):
     # Every (transport, graph) candidate that passes the bitwise gate gets a short timed trial on
     # the full problem; the fastest is timed for real. With one candidate there is no trial.
     transports = [a.transport]
-    if env and a.transport == "auto":
+    if env and a.transport == "auto" and full:
         # rccl (p2p kernels), ipc (pulls by the runtime's blit kernels), ipc_sdma (pulls by the
         # SDMA engines: no CUs taken from the interior sweep, lower bandwidth on one device)
         # (rccl_fold: rccl with the folded lower boundary, which rccl does not run by default; gated
@@ -680,7 +761,9 @@ def main(argv=None):
         transports = ["rccl", "rccl_fold", "ipc", "ipc_sdma"] if hip else ["torch"]
     elif not env:
         transports = [a.transport if a.transport in ("loopback", "host") else "auto"]
-    graphs = {"on": [True], "off": [False]}.get(a.graph, [False, True] if hip else [False])
+    # (a plain run: the engine's own transport for "auto"; replayed cycles in one process, which
+    # the trials of --full pick there, eager launches across processes, where no gate has run)
+    graphs = {"on": [True], "off": [False]}.get(a.graph, [False, True] if (hip and full) else [hip and not env])
     # (captured cycles never fold and pencils never fold, so rccl_fold is an eager z-slab candidate)
     cands = [(t, g, q) for t in transports for q in pys for g in graphs if not (t == "rccl_fold" and (g or q > 1))]
     if hip and a.graph == "auto" and len(graphs) > 1:
@@ -692,10 +775,10 @@ def main(argv=None):
     if a.rounds != "auto":
         rounds = [int(a.rounds)]
     else:
-        rounds = [2, 1] if (hip and env and world > 1) else [0]
+        rounds = [2, 1] if (full and hip and env and world > 1) else [0]
     gate = None
     t_sel0 = time.time()  # gate + trials start (the --trial-budget clock)
-    if env and world > 1 and not a.no_gate:
+    if full and env and world > 1 and not a.no_gate:
         recs, ok = [], []
         for t, g, q in cands:
             if g and (t, False, q) in cands and (t, False, q) not in ok:
@@ -729,7 +812,8 @@ def main(argv=None):
     # the round count and the overlap mode need no gate of their own (scheduling only; the
     # overlapped == serialised equality is a test). Several processes: interior || boundary +
     # exchange (overlap) against one full sweep after the exchange, whichever the trial finds faster.
-    overlaps = [True, False] if (hip and env and world > 1 and not a.no_overlap and not a.overlap) else [not a.no_overlap]
+    overlaps = [True, False] if (full and hip and env and world > 1 and not a.no_overlap and not a.overlap) \
+        else [not a.no_overlap]
     cands = [(t, g, r, ov, q) for t, g, q in cands for r in rounds for ov in overlaps]
     kw = dict(device="hip" if hip else "cpu", overlap=not a.no_overlap,
               residual_every=a.residual_every, timeout_s=timeout, temporal=temporal)
@@ -823,6 +907,13 @@ def main(argv=None):
     trace("init done (%d graph cycles captured)" % n_graphs)
     sim.run(a.warmup)
     trace("warmup enqueued")
+    # a plain run has no trials before it and one repetition: the settling passes (untimed
+    # repetitions of --steps steps) put the timed one where --full's median repetition is
+    settle_steps = 0
+    if hip and not full and a.steps > 0:
+        settle_steps = a.steps * -(-SETTLE_MIN_STEPS // a.steps)
+        for _ in range(settle_steps // a.steps):
+            sim.run(a.steps)
     timed(sim, 0)
     trace("warmup done")
     inject_timed_fault(sim, rank, world)
@@ -833,8 +924,11 @@ def main(argv=None):
         dts.append(timed(sim, a.steps))
         trace("timed %.4f s" % dts[-1])
     best = statistics.median(dts)  # the median repetition (back to back, same engine)
+    if a.dump_outputs:
+        trace("writing the outputs of the last timed step")
+        dump_outputs(a, sim, prob, env, world, rank)
     verified = None
-    if not a.no_verify:
+    if full and not a.no_verify:
         trace("verifying the timed run")
         verified = verify_timed(a, sim, prob, hip, env, rank, world, [a.warmup] + [a.steps] * repeats)
         trace("verified: %s" % verified)
@@ -851,7 +945,7 @@ def main(argv=None):
             return 4
 
     phases = links = None
-    if env and world > 1 and not a.no_diagnose:
+    if full and env and world > 1 and not a.no_diagnose:
         trace("diagnostic pass")
         phases, links = diagnose(sim, temporal, env, world, rank)
 
@@ -894,6 +988,8 @@ def main(argv=None):
             "warmup": a.warmup,
             "ms_per_step": round(ms, 4),
             "higher_is_better": True,
+            "full": full,
+            "settle_steps": settle_steps,
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": {"f32": "fp32", "f64": "fp64", "u8": "u8"}[a.dtype],
@@ -940,7 +1036,8 @@ def main(argv=None):
         }
         # the achievable-copy yardstick: torch copy_ of one GPU's share of the field (outside the timed
         # region; a fused sweep moves exactly these bytes per `temporal` steps)
-        copy_tbps = measure_copy_tbps(cells / max(ngpu_phys, 1) * prob.bytes_per_cell_per_step / 2) if hip else None
+        copy_tbps = measure_copy_tbps(cells / max(ngpu_phys, 1) * prob.bytes_per_cell_per_step / 2) \
+            if (hip and full) else None
         rec["measured_copy_TBps"] = round(copy_tbps, 3) if copy_tbps else None
         rec["pct_of_measured_copy"] = round(100.0 * dram_tbps / copy_tbps, 1) if copy_tbps else None
         rec["wall_s"] = round(time.time() - _T_START, 2)  # the whole bench process so far (gate, trials, timing, checks)

@@ -35,13 +35,13 @@ for s in "$@"; do
     ipc) run 600 ipc $PYT tests/test_gpu_ipc.py ;;
     gputests) run 1100 gputests $PYT -m gpu tests --deselect tests/test_gpu_ipc.py ;;
     smoke) run 300 smoke python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 300 bench python bench.py ;;
-    bench_t1) run 300 bench_t1 python bench.py --temporal 1 ;;
-    bench_v8) run 300 bench_v8 python bench.py --virtual-ranks 8 ;;
-    bench_ipc2) run 300 bench_ipc2 python bench.py --gpus 2 --share-gpu --transport ipc ;;
-    bench_ipc4) run 300 bench_ipc4 python bench.py --gpus 4 --share-gpu --transport ipc ;;
+    bench) run 300 bench python bench.py --full ;;
+    bench_t1) run 300 bench_t1 python bench.py --full --temporal 1 ;;
+    bench_v8) run 300 bench_v8 python bench.py --full --virtual-ranks 8 ;;
+    bench_ipc2) run 300 bench_ipc2 python bench.py --full --gpus 2 --share-gpu --transport ipc ;;
+    bench_ipc4) run 300 bench_ipc4 python bench.py --full --gpus 4 --share-gpu --transport ipc ;;
     bench_refuse) run 120 bench_refuse bash -c 'python bench.py --gpus 2 --n 256; test $? -eq 2' ;;  # must refuse
-    rccl2) run 150 rccl2 python bench.py --gpus 2 --share-gpu --transport rccl --n 256 --steps 4 --warmup 2 ;;
+    rccl2) run 150 rccl2 python bench.py --full --gpus 2 --share-gpu --transport rccl --n 256 --steps 4 --warmup 2 ;;
     prof)  # kernel trace + stats of one bench run (PROF_TAG names it, BENCH_ARGS replaces the bench flags)
       out="prof${PROF_TAG:+_$PROF_TAG}"
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats \

@@ -143,7 +143,7 @@ def test_bench_self_launches_ranks_cpu(mdfx):
     gates the decomposed engine bitwise against a full-grid run, and reports n_gpus = N."""
     import json
 
-    rc, out, err = _bench(["--device", "cpu", "--gpus", "3", "--n", "32", "--steps", "2", "--warmup", "1"])
+    rc, out, err = _bench(["--full", "--device", "cpu", "--gpus", "3", "--n", "32", "--steps", "2", "--warmup", "1"])
     assert rc == 0, err
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out
@@ -161,7 +161,7 @@ def test_bench_self_launches_8_ranks_cpu(mdfx):
     only ever meant 2 ranks, MDF_kernel.cu:29,37,155,189)."""
     import json
 
-    rc, out, err = _bench(["--device", "cpu", "--gpus", "8", "--n", "64", "--steps", "4", "--warmup", "1"],
+    rc, out, err = _bench(["--full", "--device", "cpu", "--gpus", "8", "--n", "64", "--steps", "4", "--warmup", "1"],
                           env_extra={"OMP_NUM_THREADS": "1"}, timeout=600)
     assert rc == 0, err
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -205,7 +205,7 @@ def test_bench_n1_times_three_repeats_and_reports_the_median(mdfx):
     import json
     import statistics
 
-    rc, out, err = _bench(["--device", "cpu", "--n", "24", "--steps", "3", "--warmup", "1"])
+    rc, out, err = _bench(["--full", "--device", "cpu", "--n", "24", "--steps", "3", "--warmup", "1"])
     assert rc == 0, err
     rec = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     cfg = rec["config"]
@@ -213,6 +213,53 @@ def test_bench_n1_times_three_repeats_and_reports_the_median(mdfx):
     assert len(reps) == 3 and rec["ms_per_step"] == round(statistics.median(reps), 4)
     assert cfg["verified"]["steps"] == [1, 3, 3, 3] and cfg["verified"]["passed"]
     assert cfg["phases"] is None and cfg["links"] is None and rec["wall_s"] > 0
+
+
+def _bench_json(out):
+    import json
+
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_the_steps_once_and_nothing_else(mdfx, tmp_path):
+    """Without --full: one timed repetition of exactly --steps steps, no gate, trials, verification,
+    diagnostics or copy yardstick (their JSON fields are null / empty), and --dump-outputs writes the
+    whole (small) grid after warm-up + steps, bitwise what the engine computes in process."""
+    d = str(tmp_path / "dump")
+    rc, out, err = _bench(["--device", "cpu", "--n", "24", "--steps", "3", "--warmup", "1", "--dump-outputs", d])
+    assert rc == 0, err
+    rec = _bench_json(out)
+    cfg = rec["config"]
+    assert rec["full"] is False and rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["settle_steps"] == 0
+    assert cfg["repeats_ms_per_step"] == [rec["ms_per_step"]]
+    assert cfg["verified"] is None and cfg["gate"] is None and cfg["trials"] == [] and cfg["phases"] is None
+    assert rec["measured_copy_TBps"] is None
+    got = np.load(os.path.join(d, "field.npy"))
+    assert sorted(os.listdir(d)) == ["field.npy"] and got.dtype == np.float32
+    with mdfx.Simulation(mdfx.heat3d(n=24), device="cpu") as sim:
+        ref = sim.init().run(4).gather()
+    assert np.array_equal(got, ref)
+
+
+def test_bench_dump_outputs_samples_a_large_grid_with_a_fixed_seed(mdfx, tmp_path):
+    """Above 4 Mi cells --dump-outputs writes the field at 4 Mi seeded cell indices (the same ones on
+    every run), here of a 2-rank fp64 run with a residual, which is written too."""
+    d = str(tmp_path / "dump")
+    rc, out, err = _bench(["--device", "cpu", "--gpus", "2", "--stencil", "jacobi5", "--dtype", "f64", "--nx", "4096",
+                           "--nz", "1032", "--steps", "2", "--warmup", "1", "--residual-every", "3",
+                           "--dump-outputs", d])
+    assert rc == 0, err
+    assert _bench_json(out)["n_gpus"] == 2
+    got = np.load(os.path.join(d, "field.npy"))
+    assert got.dtype == np.float64 and got.shape == (4 << 20,) and got.nbytes <= 64 << 20
+    with mdfx.Simulation(mdfx.mdf2d(h=1032, w=4096, dtype="f64"), device="cpu", residual_every=3) as sim:
+        ref = sim.init().run(3).gather()
+        res = sim.residual
+    idx = np.sort(np.random.default_rng(1).integers(0, ref.size, 4 << 20, dtype=np.int64))
+    assert np.array_equal(got, ref.reshape(-1)[idx])
+    assert np.load(os.path.join(d, "residual.npy")) == pytest.approx(res, rel=1e-9)
 
 
 def test_ipc_export_retry_loop_cpu(mdfx):
@@ -247,7 +294,7 @@ def test_bench_refuses_more_gpus_than_visible(mdfx):
 def test_bench_gate_catches_a_broken_rank(mdfx):
     """A NaN injected into rank 1 during the gate run makes the gate fail on every rank and the
     bench exit non-zero without printing a number."""
-    rc, out, err = _bench(["--device", "cpu", "--gpus", "2", "--n", "32", "--steps", "2", "--warmup", "1"],
+    rc, out, err = _bench(["--full", "--device", "cpu", "--gpus", "2", "--n", "32", "--steps", "2", "--warmup", "1"],
                           env_extra={"MDFX_FAULT": "nan@1:2"})
     assert rc != 0, out
     assert "gate FAILED" in err or "gate" in err
@@ -258,7 +305,7 @@ def test_bench_verification_catches_a_fault_the_gate_missed(mdfx):
     """MDFX_FAULT=ghost@1:timed corrupts one ghost cell of rank 1 only after the timed run's warm-up:
     the gate passes, the verification of the timed run against the full-grid run fails on the ranks
     the fault reaches, and the bench exits non-zero without printing a number."""
-    rc, out, err = _bench(["--device", "cpu", "--gpus", "2", "--n", "32", "--steps", "4", "--warmup", "1"],
+    rc, out, err = _bench(["--full", "--device", "cpu", "--gpus", "2", "--n", "32", "--steps", "4", "--warmup", "1"],
                           env_extra={"MDFX_FAULT": "ghost@1:timed"})
     assert rc != 0, out
     assert "injected a ghost-plane fault" in err

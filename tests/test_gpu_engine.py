@@ -368,3 +368,33 @@ def test_pencil_headline_shape_matches_slabs(hip):
             sim.init().run(8)
             outs.append(sim.gather())
     assert np.array_equal(outs[0], outs[1])
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(hip, tmp_path):
+    """bench.py without --full on the GPU: exactly --steps timed steps in one repetition after the
+    warm-up and whole untimed settling passes of at least 100 steps, nothing else measured, and
+    --dump-outputs holds the fused sweeps' field after all of them at the seeded sample of cells,
+    bitwise equal to single steps in process (1024-cell rows: heat7_wxk)."""
+    import json
+    import subprocess
+    import sys
+
+    d = str(tmp_path / "dump")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MDFX_FORCE_DIST")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nx", "1024", "--ny", "64",
+                        "--nz", "80", "--steps", "7", "--warmup", "3", "--dump-outputs", d],
+                       env=env, capture_output=True, timeout=120, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    rec = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])
+    cfg = rec["config"]
+    assert rec["full"] is False and rec["steps"] == 7 and cfg["temporal_block"] == 5
+    assert cfg["repeats_ms_per_step"] == [rec["ms_per_step"]] and cfg["trials"] == [] and cfg["verified"] is None
+    # (replay is asked for, as the trials of --full choose in one process; 7 steps are no whole cycle of
+    # two 5-step sweeps, so these ran eagerly, and nothing was captured inside the timed region)
+    assert rec["measured_copy_TBps"] is None and cfg["graph_requested"] is True and cfg["graph_captures_timed"] == 0
+    assert rec["settle_steps"] == 105
+    got = np.load(os.path.join(d, "field.npy"))
+    assert got.dtype == np.float32 and got.shape == (4 << 20,)
+    ref, _ = _run(m.heat3d(nx=1024, ny=64, nz=80), 3 + 105 + 7, temporal=1)
+    idx = np.sort(np.random.default_rng(1).integers(0, ref.size, 4 << 20, dtype=np.int64))
+    assert np.array_equal(got, ref.reshape(-1)[idx])

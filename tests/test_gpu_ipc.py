@@ -231,7 +231,7 @@ def test_ipc_other_stencils(hip, tmp_path, prob_src):
 def test_bench_self_launch_ipc_one_gpu(hip):
     """bench.py --gpus 2 with no launcher on a 1-GPU box: refused unless --share-gpu; with it, two
     ranks share cuda:0 over the ipc transport, pass the bitwise gate and report n_gpus = 2."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "256", "--steps", "4", "--warmup", "2"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "256", "--steps", "4", "--warmup", "2"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     import torch
 
@@ -286,7 +286,7 @@ def test_ipc_slabs_larger_than_2gib(hip):
     ipc_probe.py), so the transport exports only small face mailboxes: this run must finish."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--transport",
-                        "ipc", "--n", "1024", "--steps", "4", "--warmup", "2", "--timeout", "30"],
+                        "ipc", "--n", "1024", "--steps", "4", "--warmup", "2", "--timeout", "30", "--full"],
                        env=env, capture_output=True, timeout=170, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     rec = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])
@@ -299,7 +299,7 @@ def test_ipc_direct_protocol_at_the_headline_size(hip):
     each other's faces straight out of them (the direct protocol of the N >= 4 runs)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-gpu", "--transport",
-                        "ipc", "--n", "1024", "--steps", "8", "--warmup", "4", "--timeout", "30"],
+                        "ipc", "--n", "1024", "--steps", "8", "--warmup", "4", "--timeout", "30", "--full"],
                        env=env, capture_output=True, timeout=170, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     rec = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])

@@ -101,7 +101,7 @@ def test_bench_distributed_rccl_world1(hip):
 
 def test_bench_staged_two_processes(hip):
     outs = _spawn(2, lambda r: [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "256", "--steps", "4",
-                                "--warmup", "2", "--gpus", "2", "--transport", "staged", "--share-gpu"],
+                                "--warmup", "2", "--gpus", "2", "--transport", "staged", "--share-gpu", "--full"],
                   env_extra={"HIP_VISIBLE_DEVICES": "0"})
     lines = [l for l in outs[0].splitlines() if l.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 2
@@ -167,8 +167,8 @@ def test_bench_rccl_bootstrap_hang_exits_nonzero(hip):
     env["MDFX_FAULT"] = "inithang@1"
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--n", "128",
-                        "--steps", "4", "--warmup", "2", "--timeout", "8"], env=env, capture_output=True, timeout=400,
-                       cwd=ROOT)
+                        "--steps", "4", "--warmup", "2", "--timeout", "8", "--full"], env=env, capture_output=True,
+                       timeout=400, cwd=ROOT)
     took = time.time() - t0
     assert p.returncode != 0, p.stdout.decode()
     assert not [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -182,8 +182,8 @@ def test_bench_auto_fallback_to_staged(hip):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["MDFX_FAULT"] = "gate:rccl,ipc,ipc_sdma"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--n", "128",
-                        "--steps", "4", "--warmup", "2", "--graph", "off"], env=env, capture_output=True, timeout=280,
-                       cwd=ROOT)
+                        "--steps", "4", "--warmup", "2", "--graph", "off", "--full"], env=env, capture_output=True,
+                       timeout=280, cwd=ROOT)
     out = p.stdout.decode()
     assert p.returncode == 0, out + p.stderr.decode()
     rec = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
