@@ -71,6 +71,8 @@ def main():
         prob = m.box27(nx=nx, ny=ny, nz=nz, dtype=a.dtype)
     elif a.kind == "jacobi5":
         prob = m.mdf2d(h=nz, w=nx, dtype=a.dtype)
+    elif a.kind == "box9":
+        prob = m.box9(h=nz, w=nx, dtype=a.dtype)
     else:
         prob = m.life2d(h=nz, w=nx)
     variants = [v for v in a.variants.split(";") if v]

@@ -28,7 +28,7 @@ struct Opts {
   std::string init;
   uint64_t seed = 1;
   double lo = 0, hi = 1, value = 0, edge = 100, interior = 0, density = 0.15;
-  double r = -1, c0 = 0.25, c1 = 0.05, c2 = 0.025, c3 = 3.0 / 160.0;
+  double r = -1, c0 = NAN, c1 = NAN, c2 = NAN, c3 = 3.0 / 160.0;  // c0..c2: NAN = the stencil's default
   int residual_every = 0;
   bool print = false, json = false, sync_debug = false, overlap = true, graph = false;
   bool verbose = false, quiet = false, share_gpu = false;
@@ -50,7 +50,8 @@ void usage(const char* prog) {
   std::printf(
       "usage: %s [options]\n"
       "  With no size/step options the reference dialogue runs on stdin (generations, height, width).\n"
-      "  --stencil 5|7|27|life     stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt)\n"
+      "  --stencil 5|7|9|27|life   stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
+      "                            9 = 2D 9-pt with --c0 --c1 --c2, default 1/3, 2/15, 1/30)\n"
       "  --n N | --nx --ny --nz    3D grid (N^3) ; 2D: --h ROWS --w COLS\n"
       "  --steps K (--iters, -g)   time steps / generations ; --warmup W untimed steps first\n"
       "  --dtype f32|f64           element type (life is always u8)\n"
@@ -247,9 +248,11 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     spec.kind = kind;
     spec.dtype = kind == StencilKind::Life ? DType::U8 : dtype_from_name(o.dtype.empty() ? "f32" : o.dtype);
     spec.coef.r = o.r;
-    spec.coef.c0 = o.c0;
-    spec.coef.c1 = o.c1;
-    spec.coef.c2 = o.c2;
+    // weights not given: the 27-point's 1/4, 1/20, 1/40; the 9-point's 1/3, 2/15, 1/30
+    const bool b9 = kind == StencilKind::Box9;
+    spec.coef.c0 = !std::isnan(o.c0) ? o.c0 : (b9 ? 1.0 / 3.0 : 0.25);
+    spec.coef.c1 = !std::isnan(o.c1) ? o.c1 : (b9 ? 2.0 / 15.0 : 0.05);
+    spec.coef.c2 = !std::isnan(o.c2) ? o.c2 : (b9 ? 1.0 / 30.0 : 0.025);
     spec.coef.c3 = o.c3;
     // the reference dialogue reproduces the reference's arithmetic too (MDF_kernel.cu:20, D17)
     spec.coef.ref_precision = kind == StencilKind::Jacobi5 && (o.ref_precision || o.compat);
@@ -333,7 +336,7 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     // ---- initial condition ----------------------------------------------------------------
     std::string ik = o.init;
     if (ik.empty())
-      ik = kind == StencilKind::Jacobi5 ? "dirichlet"
+      ik = (kind == StencilKind::Jacobi5 || kind == StencilKind::Box9) ? "dirichlet"
                                         : (kind == StencilKind::Life ? (o.compat ? "compat" : "life") : "random");
     if (!o.resume.empty()) {
       solver.load_checkpoint(o.resume);

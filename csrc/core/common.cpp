@@ -78,6 +78,7 @@ const char* stencil_name(StencilKind k) {
     case StencilKind::Life: return "life";
     case StencilKind::Heat7: return "heat7";
     case StencilKind::Box27: return "box27";
+    case StencilKind::Box9: return "box9";
   }
   return "?";
 }
@@ -87,7 +88,8 @@ StencilKind stencil_from_name(const std::string& s) {
   if (s == "life" || s == "gol") return StencilKind::Life;
   if (s == "heat7" || s == "7" || s == "jacobi7" || s == "7pt") return StencilKind::Heat7;
   if (s == "box27" || s == "27" || s == "27pt") return StencilKind::Box27;
-  MDFX_FAIL("unknown stencil '" + s + "' (5|7|27|life)");
+  if (s == "box9" || s == "9" || s == "9pt") return StencilKind::Box9;
+  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|life)");
 }
 
 FieldLayout FieldLayout::make(Extent3 g, int64_t z0, int64_t z1, int halo, DType dt, int64_t y0, int64_t y1, int hy) {

@@ -130,6 +130,35 @@ void box27_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const S
   if (RES) *resid += acc;
 }
 
+// 2D 9-point: per-row partials exactly as stencil_math.hpp / the device kernels
+template <class T, bool RES>
+void box9_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const StencilCoef& cf, double* resid) {
+  const T c0 = (T)cf.c0, c1 = (T)cf.c1, c2 = (T)cf.c2;
+  double acc = 0.0;
+#pragma omp parallel for schedule(static) reduction(+ : acc) if ((le - lb) * g.nx > 262144)
+  for (int64_t lz = lb; lz < le; ++lz) {
+    const int64_t gz = lz + g.gz_off;
+    const T* __restrict__ c = in + lz * g.plane;
+    T* __restrict__ o = out + lz * g.plane;
+    if (gz > 0 && gz < g.gnz - 1 && g.nx > 2) {
+      const T *__restrict__ zm = c - g.plane, *__restrict__ zp = c + g.plane;
+      o[0] = c[0];
+#pragma omp simd
+      for (int64_t x = 1; x < g.nx - 1; ++x) {
+        const T am = sm::box9_A<T>(zm[x], zm[x - 1] + zm[x + 1], c1, c2);
+        const T bc = sm::box9_B<T>(c[x], c[x - 1] + c[x + 1], c0, c1);
+        const T ap = sm::box9_A<T>(zp[x], zp[x - 1] + zp[x + 1], c1, c2);
+        o[x] = sm::box9_combine<T>(am, bc, ap);
+      }
+      o[g.nx - 1] = c[g.nx - 1];
+    } else {
+      std::memcpy(o, c, (size_t)g.nx * sizeof(T));
+    }
+    if (RES) acc += row_resid(o, c, g.nx);
+  }
+  if (RES) *resid += acc;
+}
+
 template <bool RES>
 void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t le, double* resid) {
   double acc = 0.0;
@@ -187,6 +216,12 @@ void region_t(const StencilSpec& spec, const RegionArgs& a) {
         box27_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       else
         box27_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      break;
+    case StencilKind::Box9:
+      if (spec.dtype == DType::F32)
+        box9_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      else
+        box9_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       break;
     case StencilKind::Life:
       life_cpu<RES>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, a.resid);

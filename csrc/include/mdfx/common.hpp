@@ -50,13 +50,17 @@ enum class StencilKind : int {
   Life = 1,     // 2D Moore-8 B3/S23 Game of Life (reference kernel.cu:66)
   Heat7 = 2,    // 3D 7-point heat / Jacobi (BASELINE.json configs 2, 3, 5)
   Box27 = 3,    // 3D 27-point weighted stencil (BASELINE.json config 4)
+  Box9 = 4,     // 2D 9-point weighted stencil (centre, edge and corner weights)
 };
 const char* stencil_name(StencilKind k);
 StencilKind stencil_from_name(const std::string& s);
-inline bool stencil_is_2d(StencilKind k) { return k == StencilKind::Jacobi5 || k == StencilKind::Life; }
+inline bool stencil_is_2d(StencilKind k) {
+  return k == StencilKind::Jacobi5 || k == StencilKind::Life || k == StencilKind::Box9;
+}
 
 // Coefficients. Jacobi5/Heat7: u' = u + r * (sum_neighbours - 2d * u). Box27:
-// u' = c0*u + c1*sum(6 faces) + c2*sum(12 edges) + c3*sum(8 corners).
+// u' = c0*u + c1*sum(6 faces) + c2*sum(12 edges) + c3*sum(8 corners). Box9:
+// u' = c0*u + c1*sum(4 edges) + c2*sum(4 corners) (c3 unused).
 struct StencilCoef {
   double r = -1.0;  // < 0 -> default 1/(2d) (Jacobi)
   double c0 = 0.25, c1 = 1.0 / 20.0, c2 = 1.0 / 40.0, c3 = 3.0 / 160.0;

@@ -68,6 +68,25 @@ MDFX_HDI T box27_combine(T a_m, T b_c, T a_p) {
   return (a_m + b_c) + a_p;
 }
 
+// 2D 9-point (rows are the z axis) as a sum of per-row partials, box27 one dimension down. For one
+// row and one column x: c = v(x), h = v(x-1) + v(x+1);
+//   A (what the row gives the rows above and below) = c2*h + c1*c
+//   B (what the row gives itself)                   = c1*h + c0*c
+//   u'(z) = (A(z-1) + B(z)) + A(z+1)
+// which equals c0*u + c1*edges(4) + c2*corners(4).
+template <class T>
+MDFX_HDI T box9_A(T c, T h, T c1, T c2) {
+  return fmaT(c2, h, c1 * c);
+}
+template <class T>
+MDFX_HDI T box9_B(T c, T h, T c0, T c1) {
+  return fmaT(c1, h, c0 * c);
+}
+template <class T>
+MDFX_HDI T box9_combine(T a_m, T b_c, T a_p) {
+  return (a_m + b_c) + a_p;
+}
+
 // Life: T = sum of the 3x3 block including self.
 MDFX_HDI unsigned char life_rule(unsigned t, unsigned char alive) {
   return (unsigned char)((t == 3u) | ((t == 4u) & (alive != 0)));

@@ -36,6 +36,9 @@ bool box27_tb2_supported(const Geo& g);
 template <class T>
 void launch_box27(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid,
                   hipStream_t s);
+// 2D 9-point: box9_wave (steps = 1) and box9_tbk (2, 3, 4, 6, 8 fused steps), stencil_box9.hip
+template <class T>
+void launch_box9(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
 void launch_life(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tb2(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tbk(const Geo& g, const uint8_t* in, uint8_t* out, int steps, double* resid, hipStream_t s);
@@ -254,6 +257,7 @@ bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int ste
   const bool k2d = steps == 2 || steps == 3 || steps == 4 || steps == 6 || steps == 8;
   if (spec.kind == StencilKind::Jacobi5)  // deep temporal blocking of the 2D problems
     return (spec.dtype == DType::F32 || spec.dtype == DType::F64) && k2d;  // ref precision too (jacobi5_tbk REF)
+  if (spec.kind == StencilKind::Box9) return k2d;  // box9_tbk
   if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;  // 12 / 16: life_bits
   if (spec.kind == StencilKind::Heat7 && steps > 2) {  // deep temporal blocking (rows within one block)
     if (dev::use_wtk(steps, spec.dtype)) return true;
@@ -281,6 +285,12 @@ bool hip_region_signals(const StencilSpec& spec, const FieldLayout& lay, int ste
 int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
   switch (spec.kind) {
     case StencilKind::Jacobi5: return 8;
+    case StencilKind::Box9:
+      // the deepest sweep is the fastest per step for both dtypes: 16384^2 fp32 557 / 1166 / 1640 /
+      // 2177 / 3462 / 3607 GCells/s for K = 1 / 2 / 3 / 4 / 6 / 8 (jacobi5 in the same call: 576 /
+      // 1123 / 1706 / 2277 / 3400 / 4611), fp64 281 / 564 / 835 / 1104 / 1759 / 1901 (304 / 613 / 904 /
+      // 1203 / 1639 / 2276); the sweeps stay at the memory roof up to K = 6 (profiles/r07_box9/)
+      return 8;
     case StencilKind::Life: return 12;
     case StencilKind::Box27:
       // K = 3 through box27_wxk for fp64 (512^3: 663 vs 527 GCells/s for box27_tbk K = 2), for fp32
@@ -336,6 +346,16 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
     static const double f64w[6] = {0.0, 1.0, 1.27, 1.16, 1.41, 1.55};
     if (spec.dtype == DType::F64) return (nx >= 2048 ? f64w : f64)[steps];
     return f32[steps];
+  }
+  if (spec.kind == StencilKind::Box9 && steps <= 8 && nx >= 8192) {
+    // per-sweep times against a single step at 16384^2 (profiles/r07_box9/): a sweep of up to 6 steps
+    // costs one pass over memory, K = 8 is bound by its arithmetic. (The default's 1.25 / 1.35 for
+    // K = 6 / 8 cuts a 9-step residual interval into 8 + 1, 2.24 single-step times by these figures
+    // against 1.99 for 6 + 3.)
+    static const double f32[9] = {0.0, 1.0, 0.96, 1.02, 1.02, 0.0, 0.97, 0.0, 1.24};
+    static const double f64[9] = {0.0, 1.0, 1.00, 1.01, 1.02, 0.0, 0.96, 0.0, 1.18};
+    const double c = (spec.dtype == DType::F64 ? f64 : f32)[steps];
+    if (c > 0.0) return c;
   }
   return 1.0 + 0.05 * (steps - 1);
 }
@@ -414,6 +434,11 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
         dev::launch_box27_tb2<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.resid, s);
       else
         dev::launch_box27_tb2<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.resid, s);
+    } else if (spec.kind == StencilKind::Box9) {
+      if (spec.dtype == DType::F32)
+        dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
+      else
+        dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
     } else if (spec.kind == StencilKind::Life) {
       if (a.steps > 2)
         dev::launch_life_tbk(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.steps, a.resid, s);
@@ -484,6 +509,12 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
           dev::launch_box27<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.resid, s);
         else
           dev::launch_box27<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.resid, s);
+        break;
+      case StencilKind::Box9:
+        if (spec.dtype == DType::F32)
+          dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
+        else
+          dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
         break;
       case StencilKind::Life:
         dev::launch_life(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.resid, s);

@@ -134,6 +134,9 @@ __global__ __launch_bounds__(256) void naive_life(const uint8_t* __restrict__ in
   if (RES) wave_atomic_add(resid, acc);
 }
 
+template <class T>
+void launch_box9_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
+
 static int naive_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (int)std::min<int64_t>(std::max<int64_t>(b, 1), 256 * 32);
@@ -173,6 +176,12 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
         MDFX_NAIVE(naive_box27, double, c.c0, c.c1, c.c2, c.c3);
       break;
     }
+    case StencilKind::Box9:  // (the kernel lives in stencil_box9.hip, built without packed fp32 ops)
+      if (spec.dtype == DType::F32)
+        launch_box9_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
+      else
+        launch_box9_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
+      break;
     case StencilKind::Life:
       if (res)
         hipLaunchKernelGGL(naive_life<true>, grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid);

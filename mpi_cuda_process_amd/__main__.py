@@ -21,7 +21,7 @@ from .utils import metrics_record, print_array
 
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m mpi_cuda_process_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("--stencil", default="7", help="5 | 7 | 27 | life (aliases: mdf, heat7, box27, gol)")
+    p.add_argument("--stencil", default="7", help="5 | 7 | 9 | 27 | life (aliases: mdf, heat7, box9, box27, gol)")
     p.add_argument("--n", type=int, default=0)
     p.add_argument("--nx", type=int, default=0)
     p.add_argument("--ny", type=int, default=0)
@@ -58,11 +58,11 @@ def _problem(a):
     from .models import from_name
 
     kind = from_name(a.stencil).kind  # resolve aliases
-    if kind in ("jacobi5", "life"):
+    if kind in ("jacobi5", "life", "box9"):
         h = a.h or a.nz or a.n or 256
         w = a.w or a.nx or a.n or 256
         kw = dict(h=h, w=w)
-        if kind == "jacobi5":
+        if kind != "life":
             kw["dtype"] = a.dtype
         else:
             kw["seed"] = a.seed

@@ -9,6 +9,7 @@ the default initial condition. Families (reference parity in brackets):
   [kernel.cu:10-68 update, :131-146 initial grid]
 * :func:`heat3d`  — 3D 7-point heat / Jacobi (headline benchmark, BASELINE.json configs 2, 3, 5)
 * :func:`box27`   — 3D 27-point weighted stencil (BASELINE.json config 4)
+* :func:`box9`    — 2D 9-point weighted stencil (centre, edge and corner weights), Dirichlet edges
 
 2D grids are stored as ``nx = w, ny = 1, nz = h``: rows are the slab axis, exactly like the
 reference's row split (MDF_kernel.cu:30,54).
@@ -19,7 +20,8 @@ from __future__ import annotations
 from dataclasses import dataclass, field, replace
 from typing import Optional
 
-KINDS = ("jacobi5", "life", "heat7", "box27")
+KINDS = ("jacobi5", "life", "heat7", "box27", "box9")
+KINDS_2D = ("jacobi5", "life", "box9")
 
 
 @dataclass(frozen=True)
@@ -54,7 +56,7 @@ class Problem:
     def __post_init__(self):
         if self.kind not in KINDS:
             raise ValueError("unknown stencil kind %r (one of %s)" % (self.kind, ", ".join(KINDS)))
-        if self.kind in ("jacobi5", "life") and self.ny != 1:
+        if self.kind in KINDS_2D and self.ny != 1:
             raise ValueError("2D problems use ny == 1 (nx = width, nz = height)")
         if self.kind == "life" and self.dtype != "u8":
             raise ValueError("life cells are u8")
@@ -66,7 +68,7 @@ class Problem:
 
     @property
     def dims(self) -> int:
-        return 2 if self.kind in ("jacobi5", "life") else 3
+        return 2 if self.kind in KINDS_2D else 3
 
     @property
     def cells(self) -> int:
@@ -76,7 +78,7 @@ class Problem:
     def rate(self) -> float:
         if self.r >= 0:
             return self.r
-        return 0.25 if self.kind == "jacobi5" else 1.0 / 6.0
+        return 0.25 if self.kind in ("jacobi5", "box9") else 1.0 / 6.0
 
     @property
     def bytes_per_cell_per_step(self) -> int:
@@ -124,13 +126,23 @@ def box27(n: int = 512, nx: Optional[int] = None, ny: Optional[int] = None, nz: 
                    c3=c3, init=init or InitCondition(kind="random", seed=1))
 
 
+def box9(h: int = 256, w: int = 256, dtype: str = "f32", c0: float = 1.0 / 3.0, c1: float = 2.0 / 15.0,
+         c2: float = 1.0 / 30.0, init: Optional[InitCondition] = None) -> Problem:
+    """2D 9-point weighted stencil u' = c0 u + c1 edges + c2 corners on an h x w grid, Dirichlet edges
+    100. The default weights are u + (1/30) * (4 edges + corners - 20 u): the compact fourth-order
+    ("Mehrstellen") Laplacian's 4 : 1 proportion; they sum to 1."""
+    return Problem("box9", nx=w, ny=1, nz=h, dtype=dtype, c0=c0, c1=c1, c2=c2,
+                   init=init or InitCondition(kind="dirichlet", edge=100.0, interior=0.0))
+
+
 def from_name(kind: str, **kw) -> Problem:
     aliases = {"5": "jacobi5", "mdf": "jacobi5", "jacobi5": "jacobi5", "life": "life", "gol": "life",
-               "7": "heat7", "heat7": "heat7", "jacobi7": "heat7", "27": "box27", "box27": "box27"}
+               "7": "heat7", "heat7": "heat7", "jacobi7": "heat7", "27": "box27", "box27": "box27",
+               "9": "box9", "9pt": "box9", "box9": "box9"}
     k = aliases.get(str(kind))
     if k is None:
         raise ValueError("unknown stencil %r" % kind)
-    return {"jacobi5": mdf2d, "life": life2d, "heat7": heat3d, "box27": box27}[k](**kw)
+    return {"jacobi5": mdf2d, "life": life2d, "heat7": heat3d, "box27": box27, "box9": box9}[k](**kw)
 
 
-__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "from_name", "KINDS"]
+__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "from_name", "KINDS"]

@@ -56,6 +56,18 @@ def box27(u: torch.Tensor, c0: float = 0.25, c1: float = 1.0 / 20.0, c2: float =
     return out
 
 
+def box9(u: torch.Tensor, c0: float = 1.0 / 3.0, c1: float = 2.0 / 15.0, c2: float = 1.0 / 30.0) -> torch.Tensor:
+    """2D 9-point; ``u`` is (h, 1, w) or (h, w)."""
+    squeeze = u.dim() == 2
+    g = u if squeeze else u[:, 0, :]
+    out = g.clone()
+    if min(g.shape) >= 3:
+        edges = (g[1:-1, :-2] + g[1:-1, 2:]) + (g[:-2, 1:-1] + g[2:, 1:-1])
+        corners = (g[:-2, :-2] + g[:-2, 2:]) + (g[2:, :-2] + g[2:, 2:])
+        out[1:-1, 1:-1] = c0 * g[1:-1, 1:-1] + c1 * edges + c2 * corners
+    return out if squeeze else out.unsqueeze(1)
+
+
 def life(u: torch.Tensor) -> torch.Tensor:
     """Game of Life B3/S23 with a held (dead) frame; ``u`` is (h, 1, w) or (h, w) uint8."""
     squeeze = u.dim() == 2
@@ -85,6 +97,8 @@ def step(kind: str, u: torch.Tensor, **coef) -> torch.Tensor:
     if kind == "box27":
         return box27(u, coef.get("c0", 0.25), coef.get("c1", 0.05), coef.get("c2", 0.025),
                      coef.get("c3", 3.0 / 160.0))
+    if kind == "box9":
+        return box9(u, coef.get("c0", 1.0 / 3.0), coef.get("c1", 2.0 / 15.0), coef.get("c2", 1.0 / 30.0))
     if kind == "life":
         return life(u)
     raise ValueError(kind)
