@@ -66,6 +66,7 @@ $(OBJ)/kernels/stencil_heat_tb.o $(ASAN_DIR)/kernels/stencil_heat_tb.o $(DCK_DIR
 $(OBJ)/kernels/stencil_box27.o $(ASAN_DIR)/kernels/stencil_box27.o $(DCK_DIR)/kernels/stencil_box27.o: HIPFLAGS += -fno-slp-vectorize
 # box9 keeps its fp32 arithmetic in plain (unpacked) VALU ops
 $(OBJ)/kernels/stencil_box9.o $(ASAN_DIR)/kernels/stencil_box9.o $(DCK_DIR)/kernels/stencil_box9.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(OBJ)/kernels/stencil_life_rule.o $(ASAN_DIR)/kernels/stencil_life_rule.o $(DCK_DIR)/kernels/stencil_life_rule.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 # the AVX2 + FMA copy of the CPU stencils (selected at run time by cpu_kernels.cpp)
 $(OBJ)/cpu/cpu_kernels_avx2.o $(ASAN_DIR)/cpu/cpu_kernels_avx2.o $(DCK_DIR)/cpu/cpu_kernels_avx2.o: HOSTFLAGS += -mavx2 -mfma

@@ -10,6 +10,7 @@ bitwise against the naive kernel.
 """
 
 import argparse
+import dataclasses
 import json
 import os
 import statistics
@@ -34,9 +35,18 @@ def parse_variant(s):
             fam = v
         elif k == "STEPS":
             steps = int(v)
-        else:
+        elif k != "RULE":
             env[KEYS[k]] = v
     return fam, env, steps
+
+
+def variant_rule(s, default):
+    """RULE=B36/S23 in a variant (--kind life): that variant runs this rule, so Conway's kernels and
+    the table-driven one alternate in one process; without it the variant runs --rule."""
+    for part in filter(None, s.split(",")):
+        if part.startswith("RULE="):
+            return part[5:]
+    return default
 
 
 def apply_env(env):
@@ -57,6 +67,7 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--variants", default="FAM=naive;RY=4,PF=2")
+    p.add_argument("--rule", default="B3/S23", help="--kind life: the Life-like rule (a variant's RULE= overrides it)")
     p.add_argument("--json", default="")
     p.add_argument("--thief", type=int, default=0,
                    help="launch this many single-block spin kernels (torch.cuda._sleep, ~--thief-us) on "
@@ -74,28 +85,30 @@ def main():
     elif a.kind == "box9":
         prob = m.box9(h=nz, w=nx, dtype=a.dtype)
     else:
-        prob = m.life2d(h=nz, w=nx)
+        prob = m.life2d(h=nz, w=nx, rule=a.rule)
     variants = [v for v in a.variants.split(";") if v]
     max_steps = max(parse_variant(v)[2] for v in variants)
     lay = FieldLayout.make(prob, halo=max_steps)
     A = alloc_field(lay, "cuda")
     B = alloc_field(lay, "cuda")
-    R = alloc_field(lay, "cuda")
     init_field(prob, lay, A)
     init_field(prob, lay, B)
     set_kernel_variant("naive")
-    refs = {1: R}
-    apply_stencil(prob, lay, A, R)
-    if max_steps > 1:  # k naive single steps; the fused sweep must match them bitwise
-        R2 = alloc_field(lay, "cuda")
-        cur = R
-        for k in range(2, max_steps + 1):
+    # the problem each variant runs (the same but for a Life variant's RULE=) and, per rule, k naive
+    # single steps; the fused sweep must match them bitwise
+    probs = {v: dataclasses.replace(prob, rule=variant_rule(v, a.rule)) if a.kind == "life" else prob
+             for v in variants}
+    refs = {}
+    for pr in {p.rule: p for p in probs.values()}.values():
+        cur = alloc_field(lay, "cuda")
+        apply_stencil(pr, lay, A, cur)
+        refs[pr.rule, 1] = cur
+        for k in range(2, max(parse_variant(v)[2] for v in variants if probs[v].rule == pr.rule) + 1):
             nxt = alloc_field(lay, "cuda")
             nxt.copy_(cur)
-            apply_stencil(prob, lay, cur, nxt)
-            refs[k] = nxt
+            apply_stencil(pr, lay, cur, nxt)
+            refs[pr.rule, k] = nxt
             cur = nxt
-        del R2
     torch.cuda.synchronize()
     ok = {}
     for v in variants:
@@ -103,9 +116,9 @@ def main():
         apply_env(env)
         set_kernel_variant(fam)
         B.zero_()
-        apply_stencil(prob, lay, A, B, steps=steps)
+        apply_stencil(probs[v], lay, A, B, steps=steps)
         torch.cuda.synchronize()
-        ok[v] = bool(torch.equal(B[lay.owned, :, :nx], refs[steps][lay.owned, :, :nx]))
+        ok[v] = bool(torch.equal(B[lay.owned, :, :nx], refs[probs[v].rule, steps][lay.owned, :, :nx]))
     thieves = [torch.cuda.Stream() for _ in range(a.thief)]
     thief_cycles = int(a.thief_us * 2.4e3)  # gfx950 shader clock ~2.4 GHz
     # copy roof with the same bytes (one read + one write of the field)
@@ -127,7 +140,7 @@ def main():
             # rough data of the first ~40 steps after a random init (a data-dependent clock), so a
             # variant timed right after the init would be penalised against the ones timed later
             init_field(prob, lay, A)
-            apply_stencil(prob, lay, A, B, steps=steps)
+            apply_stencil(probs[v], lay, A, B, steps=steps)
             e0.record()
             for i in range(a.iters):
                 if thieves:
@@ -137,7 +150,7 @@ def main():
                         st.wait_event(ev)
                         with torch.cuda.stream(st):
                             torch.cuda._sleep(thief_cycles)
-                apply_stencil(prob, lay, A if i % 2 == 0 else B, B if i % 2 == 0 else A, steps=steps)
+                apply_stencil(probs[v], lay, A if i % 2 == 0 else B, B if i % 2 == 0 else A, steps=steps)
             e1.record()
             torch.cuda.synchronize()
             times[v].append(e0.elapsed_time(e1) / a.iters / steps)  # per time step
@@ -154,7 +167,7 @@ def main():
     for v in variants:
         b, md = min(times[v]), statistics.median(times[v])
         rec = {"variant": v, "best_ms": b, "median_ms": md, "gcells": cells / b / 1e6, "pct_copy": 100 * cbest / b,
-               "bitwise_vs_naive": ok[v]}
+               "bitwise_vs_naive": ok[v], "rounds_ms": times[v]}
         out["variants"].append(rec)
         print("%-28s %9.4f %9.4f %10.1f %8.1f %s" % (v, b, md, rec["gcells"], rec["pct_copy"], ok[v]))
     if a.json:

@@ -39,6 +39,7 @@ struct Opts {
   std::string ckpt_dir = "mdfx_ckpt", resume;
   bool compat = false;
   bool ref_precision = false;
+  std::string rule;  // --rule B36/S23 (Life); empty = Conway's B3/S23
   int temporal = 0;  // 0 = auto: hip_fused_depth on HIP where a fused kernel exists, else 1
   int py = 1;        // --py: ranks along y of a (z, y) pencil split
   bool profile = false;
@@ -68,6 +69,8 @@ void usage(const char* prog) {
       "  --r R | --c0 --c1 --c2 --c3   update coefficients\n"
       "  --ref-precision           2D MDF: the reference's fp32-sum / fp64-scale evaluation of the update\n"
       "                            (default in the reference dialogue; single-step sweeps)\n"
+      "  --rule B<n..>/S<n..>      Life: any outer-totalistic Moore rule, e.g. B36/S23 (HighLife),\n"
+      "                            B3678/S34678 (Day & Night), B2/S (Seeds); default B3/S23\n"
       "  --residual-every K        global L2 norm of the update every K steps\n"
       "  --checkpoint-every K --checkpoint-dir D ; --resume D\n"
       "  --print                   dump the final grid like the reference's print_array\n"
@@ -145,6 +148,7 @@ Opts parse(int argc, char** argv, const char* prog) {
     else if (a == "--timeout") o.timeout = std::atof(need(i));
     else if (a == "--compat") o.compat = true;
     else if (a == "--ref-precision") o.ref_precision = true;
+    else if (a == "--rule") o.rule = need(i);
     else if (a == "--temporal") o.temporal = std::atoi(need(i));
     else if (a == "--py") o.py = std::atoi(need(i));
     else if (a == "--profile") o.profile = true;
@@ -256,6 +260,10 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     spec.coef.c3 = o.c3;
     // the reference dialogue reproduces the reference's arithmetic too (MDF_kernel.cu:20, D17)
     spec.coef.ref_precision = kind == StencilKind::Jacobi5 && (o.ref_precision || o.compat);
+    if (!o.rule.empty()) {
+      MDFX_CHECK(kind == StencilKind::Life, "--rule goes with --stencil life");
+      life_rule_from_name(o.rule, spec.coef.birth, spec.coef.survive);
+    }
     hip_set_kernel_variant(o.variant.c_str());
 
     // ---- backend / slabs / transport ------------------------------------------------------

@@ -92,6 +92,33 @@ StencilKind stencil_from_name(const std::string& s) {
   MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|life)");
 }
 
+void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive) {
+  const auto bad = [&]() { MDFX_FAIL("bad Life rule '" + s + "' (B<digits 0-8>/S<digits 0-8>, e.g. B36/S23)"); };
+  uint32_t m[2] = {0, 0};
+  size_t i = 0;
+  for (int side = 0; side < 2; ++side) {
+    if (i >= s.size() || (s[i] | 0x20) != (side == 0 ? 'b' : 's')) bad();
+    for (++i; i < s.size() && s[i] >= '0' && s[i] <= '8'; ++i) m[side] |= 1u << (s[i] - '0');
+    if (side == 0) {
+      if (i >= s.size() || s[i] != '/') bad();
+      ++i;
+    }
+  }
+  if (i != s.size()) bad();
+  birth = m[0];
+  survive = m[1];
+}
+
+std::string life_rule_name(uint32_t birth, uint32_t survive) {
+  std::string s = "B";
+  for (int n = 0; n <= 8; ++n)
+    if (birth >> n & 1u) s += (char)('0' + n);
+  s += "/S";
+  for (int n = 0; n <= 8; ++n)
+    if (survive >> n & 1u) s += (char)('0' + n);
+  return s;
+}
+
 FieldLayout FieldLayout::make(Extent3 g, int64_t z0, int64_t z1, int halo, DType dt, int64_t y0, int64_t y1, int hy) {
   MDFX_CHECK(g.nx >= 1 && g.ny >= 1 && g.nz >= 1, "grid extents must be positive");
   MDFX_CHECK(0 <= z0 && z0 <= z1 && z1 <= g.nz, "owned plane range out of the grid");

@@ -159,8 +159,10 @@ void box9_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const St
   if (RES) *resid += acc;
 }
 
-template <bool RES>
-void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t le, double* resid) {
+// CONWAY: sm::life_rule (B3/S23); otherwise sm::life_like with the spec's two masks
+template <bool RES, bool CONWAY>
+void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t le, unsigned birth, unsigned survive,
+              double* resid) {
   double acc = 0.0;
 #pragma omp parallel for schedule(static) reduction(+ : acc) if ((le - lb) * g.nx > 1048576)
   for (int64_t lz = lb; lz < le; ++lz) {
@@ -174,7 +176,7 @@ void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t 
       for (int64_t x = 1; x < g.nx - 1; ++x) {
         const unsigned t = (unsigned)zm[x - 1] + zm[x] + zm[x + 1] + c[x - 1] + c[x] + c[x + 1] + zp[x - 1] +
                            zp[x] + zp[x + 1];
-        o[x] = sm::life_rule(t, c[x]);
+        o[x] = CONWAY ? sm::life_rule(t, c[x]) : sm::life_like(t, c[x], birth, survive);
       }
       o[g.nx - 1] = c[g.nx - 1];
     } else {
@@ -224,7 +226,11 @@ void region_t(const StencilSpec& spec, const RegionArgs& a) {
         box9_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       break;
     case StencilKind::Life:
-      life_cpu<RES>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, a.resid);
+      if (spec.conway())
+        life_cpu<RES, true>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, 0, 0, a.resid);
+      else
+        life_cpu<RES, false>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, spec.coef.birth,
+                             spec.coef.survive, a.resid);
       break;
   }
 }

@@ -68,12 +68,24 @@ struct StencilCoef {
   // -4u, fp64 scale and add, one more rounding at the store) instead of wholly in the field type.
   // See StencilSpec::mixed_update() for when the two can differ at all.
   bool ref_precision = false;
+  // Life only: the outer-totalistic Moore rule as two 9-bit masks. Bit n of `birth` set: a dead cell
+  // with n live neighbours becomes alive; bit n of `survive` set: a live cell with n live neighbours
+  // stays alive. The default is Conway's B3/S23.
+  uint32_t birth = 0x008, survive = 0x00C;
 };
+
+// A Life-like rule in B/S notation: "B36/S23", case-insensitive, digits 0..8 in any order, either
+// side may be empty ("B2/S"). Anything else throws an Error that names the text.
+void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive);
+std::string life_rule_name(uint32_t birth, uint32_t survive);  // canonical form, digits ascending
 
 struct StencilSpec {
   StencilKind kind = StencilKind::Heat7;
   DType dtype = DType::F32;
   StencilCoef coef;
+  // Conway's rule runs the B3/S23 kernels (life_wave, life_tb2, life_bits, sm::life_rule); every
+  // other rule runs the table-driven ones (life_rule_bits, sm::life_like)
+  bool conway() const { return coef.birth == 0x008u && coef.survive == 0x00Cu; }
   double rate() const {  // effective r for 5/7-pt
     if (coef.r >= 0) return coef.r;
     return kind == StencilKind::Jacobi5 ? 0.25 : 1.0 / 6.0;

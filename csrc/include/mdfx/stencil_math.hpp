@@ -92,5 +92,12 @@ MDFX_HDI unsigned char life_rule(unsigned t, unsigned char alive) {
   return (unsigned char)((t == 3u) | ((t == 4u) & (alive != 0)));
 }
 
+// Any outer-totalistic Moore rule: bit n of `birth` / `survive` decides a dead / live cell with n
+// live neighbours (n = t - alive, 0..8). life_like(t, a, 0x008, 0x00C) == life_rule(t, a).
+MDFX_HDI unsigned char life_like(unsigned t, unsigned char alive, unsigned birth, unsigned survive) {
+  const unsigned a = alive != 0;
+  return (unsigned char)(((a ? survive : birth) >> (t - a)) & 1u);
+}
+
 }  // namespace sm
 }  // namespace mdfx

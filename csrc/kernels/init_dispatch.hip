@@ -42,6 +42,9 @@ void launch_box9(const Geo& g, const T* in, T* out, const StencilCoef& c, int st
 void launch_life(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tb2(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tbk(const Geo& g, const uint8_t* in, uint8_t* out, int steps, double* resid, hipStream_t s);
+// any rule but Conway's: life_rule_bits (1, 2, 3, 4, 6, 8, 12, 16 generations), stencil_life_rule.hip
+void launch_life_rule(const Geo& g, const uint8_t* in, uint8_t* out, uint32_t birth, uint32_t survive, int steps,
+                      double* resid, hipStream_t s);
 template <class T>
 void launch_heat7_tb2(const Geo& g, const T* in, T* out, T r, double* resid, hipStream_t s);
 template <class T>
@@ -258,7 +261,8 @@ bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int ste
   if (spec.kind == StencilKind::Jacobi5)  // deep temporal blocking of the 2D problems
     return (spec.dtype == DType::F32 || spec.dtype == DType::F64) && k2d;  // ref precision too (jacobi5_tbk REF)
   if (spec.kind == StencilKind::Box9) return k2d;  // box9_tbk
-  if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;  // 12 / 16: life_bits
+  // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
+  if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;
   if (spec.kind == StencilKind::Heat7 && steps > 2) {  // deep temporal blocking (rows within one block)
     if (dev::use_wtk(steps, spec.dtype)) return true;
     const dev::Geo g = dev::make_geo(lay, lay.halo, lay.halo + lay.nzl());
@@ -291,7 +295,12 @@ int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
       // 1123 / 1706 / 2277 / 3400 / 4611), fp64 281 / 564 / 835 / 1104 / 1759 / 1901 (304 / 613 / 904 /
       // 1203 / 1639 / 2276); the sweeps stay at the memory roof up to K = 6 (profiles/r07_box9/)
       return 8;
-    case StencilKind::Life: return 12;
+    case StencilKind::Life:
+      // any other rule (life_rule_bits): 12 as well, by its own measurement. 32768^2, HighLife, GCells/s
+      // for K = 1 / 2 / 3 / 4 / 6 / 8 / 12 / 16: 2232 / 4415 / 6532 / 8584 / 12656 / 16217 / 19233 / 16380
+      // (Conway's kernels in the same call: 2438 / 4842 / 6329 / 8310 / 12157 / 16280 / 22639 / 22286);
+      // K = 16 runs at 2 waves per SIMD (177-184 VGPRs) and loses (profiles/r08_life_rules/)
+      return 12;
     case StencilKind::Box27:
       // K = 3 through box27_wxk for fp64 (512^3: 663 vs 527 GCells/s for box27_tbk K = 2), for fp32
       // rows of 1024 cells and more (1024^3: 1291 vs 1102, profiles/archive/r03_wxk/) and, since round 5's
@@ -356,6 +365,13 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
     static const double f64[9] = {0.0, 1.0, 1.00, 1.01, 1.02, 0.0, 0.96, 0.0, 1.18};
     const double c = (spec.dtype == DType::F64 ? f64 : f32)[steps];
     if (c > 0.0) return c;
+  }
+  if (spec.kind == StencilKind::Life && !spec.conway() && steps <= 16 && nx >= 8192) {
+    // life_rule_bits' per-sweep times against its own single step at 32768^2 (profiles/r08_life_rules/):
+    // one pass over memory up to K = 8, bound by its arithmetic from K = 12 on, and K = 16 (2 waves per
+    // SIMD) costs more than two sweeps of 8
+    static const double c[17] = {0.0, 1.0, 1.01, 1.03, 1.04, 0.0, 1.06, 0.0, 1.10, 0.0, 0.0, 0.0, 1.39, 0.0, 0.0, 0.0, 2.18};
+    if (c[steps] > 0.0) return c[steps];
   }
   return 1.0 + 0.05 * (steps - 1);
 }
@@ -439,6 +455,9 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
         dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
       else
         dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
+    } else if (spec.kind == StencilKind::Life && !spec.conway()) {
+      dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, a.steps,
+                            a.resid, s);
     } else if (spec.kind == StencilKind::Life) {
       if (a.steps > 2)
         dev::launch_life_tbk(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.steps, a.resid, s);
@@ -517,7 +536,11 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
           dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
         break;
       case StencilKind::Life:
-        dev::launch_life(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.resid, s);
+        if (spec.conway())
+          dev::launch_life(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.resid, s);
+        else
+          dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, 1,
+                                a.resid, s);
         break;
     }
   }

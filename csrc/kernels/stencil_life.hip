@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "kcommon.hpp"
+#include "life_pack.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
 
@@ -321,12 +322,7 @@ void launch_life_tb2(const Geo& g, const uint8_t* in, uint8_t* out, double* resi
 // Waves overlap by one lane per side (a generation corrupts one more cell of the halo lanes from the
 // outside in: K <= 32). Held cells (x = 0, x >= nx - 1, the first / last row)
 // keep their state through a per-lane bit mask. Bitwise equal to K single generations.
-__device__ __forceinline__ uint32_t life_pack4(uint32_t d) {  // bytes 0/1 -> bits 0..3
-  return __builtin_amdgcn_ubfe(d * 0x01020408u, 24, 4);
-}
-__device__ __forceinline__ uint32_t life_unpack4(uint32_t w, int k) {  // bits 4k..4k+3 -> bytes 0/1
-  return (__builtin_amdgcn_ubfe(w, 4 * k, 4) * 0x00204081u) & 0x01010101u;
-}
+// (life_pack4 / life_unpack4: life_pack.hpp, shared with life_rule_bits.)
 
 template <int K, bool RES>
 __global__ __launch_bounds__(256) void life_bits(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,

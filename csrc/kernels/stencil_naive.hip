@@ -107,10 +107,22 @@ __global__ __launch_bounds__(256) void naive_box27(const T* __restrict__ in, T* 
   if (RES) wave_atomic_add(resid, acc);
 }
 
-template <bool RES>
+// the rule of a Life kernel: Conway's fixed compare (sm::life_rule) or the two masks of any other
+// outer-totalistic rule (sm::life_like); passed last, so Conway's kernel arguments stay where they were
+struct ConwayRule {
+  __device__ unsigned char operator()(unsigned t, unsigned char c) const { return sm::life_rule(t, c); }
+};
+struct TableRule {
+  unsigned birth, survive;
+  __device__ unsigned char operator()(unsigned t, unsigned char c) const {
+    return sm::life_like(t, c, birth, survive);
+  }
+};
+
+template <bool RES, class Rule>
 __global__ __launch_bounds__(256) void naive_life(const uint8_t* __restrict__ in,
                                                   uint8_t* __restrict__ out, Geo g,
-                                                  double* __restrict__ resid) {
+                                                  double* __restrict__ resid, Rule rule) {
   const int64_t n = g.nx * (g.lz_end - g.lz_begin);
   double acc = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -126,7 +138,7 @@ __global__ __launch_bounds__(256) void naive_life(const uint8_t* __restrict__ in
       for (int dz = -1; dz <= 1; ++dz)
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx) t += in[idx + dz * g.plane + dx];
-      o = sm::life_rule(t, c);
+      o = rule(t, c);
     }
     out[idx] = o;
     if (RES) acc += (o != c) ? 1.0 : 0.0;
@@ -182,12 +194,20 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
       else
         launch_box9_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
       break;
-    case StencilKind::Life:
-      if (res)
-        hipLaunchKernelGGL(naive_life<true>, grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid);
+    case StencilKind::Life: {
+      const TableRule tr{spec.coef.birth, spec.coef.survive};
+      if (spec.conway() && res)
+        hipLaunchKernelGGL((naive_life<true, ConwayRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid,
+                           ConwayRule{});
+      else if (spec.conway())
+        hipLaunchKernelGGL((naive_life<false, ConwayRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid,
+                           ConwayRule{});
+      else if (res)
+        hipLaunchKernelGGL((naive_life<true, TableRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid, tr);
       else
-        hipLaunchKernelGGL(naive_life<false>, grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid);
+        hipLaunchKernelGGL((naive_life<false, TableRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid, tr);
       break;
+    }
   }
 #undef MDFX_NAIVE
 }

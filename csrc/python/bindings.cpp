@@ -79,9 +79,11 @@ py::capsule make_dlpack(void* data, int device, DType dt, std::vector<int64_t> s
 }
 
 StencilSpec make_spec(const std::string& kind, const std::string& dtype, double r, double c0,
-                      double c1, double c2, double c3, bool ref_precision = false) {
+                      double c1, double c2, double c3, bool ref_precision = false,
+                      const std::string& rule = "B3/S23") {
   StencilSpec s;
   s.coef.ref_precision = ref_precision;
+  life_rule_from_name(rule, s.coef.birth, s.coef.survive);
   s.kind = stencil_from_name(kind);
   s.dtype = dtype_from_name(dtype);
   s.coef.r = r;
@@ -206,8 +208,9 @@ class PySolver {
            int nranks, std::vector<int> local_ranks, std::vector<int> devices,
            const std::string& transport, py::bytes unique_id, py::object callbacks, bool overlap,
            bool sync_debug, int residual_every, bool graph, double timeout_s, double r, double c0,
-           double c1, double c2, double c3, int temporal, bool ref_precision, int pencil_py, bool share_gpu) {
-    const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision);
+           double c1, double c2, double c3, int temporal, bool ref_precision, int pencil_py, bool share_gpu,
+           const std::string& rule) {
+    const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule);
     if (devices.size() == 1 && local_ranks.size() > 1) devices.assign(local_ranks.size(), devices[0]);
     if (devices.size() != local_ranks.size())
       throw Error("devices must have one entry per local rank (or a single entry)");
@@ -330,7 +333,7 @@ PYBIND11_MODULE(_mdfx, m) {
       [](const std::string& kind, const std::string& dtype, uintptr_t in, uintptr_t out, int64_t nx,
          int64_t ny, int64_t nz, int64_t z0, int64_t z1, int halo, int64_t lz_begin, int64_t lz_end,
          int device, uintptr_t stream, uintptr_t resid, double r, double c0, double c1, double c2,
-         double c3, int steps, bool ref_precision, int64_t lz2_begin, int64_t lz2_end) {
+         double c3, int steps, bool ref_precision, int64_t lz2_begin, int64_t lz2_end, const std::string& rule) {
         RegionArgs a;
         a.lz2_begin = lz2_begin;
         a.lz2_end = lz2_end;
@@ -341,7 +344,7 @@ PYBIND11_MODULE(_mdfx, m) {
         a.lz_end = lz_end;
         a.resid = (double*)resid;
         a.steps = steps;
-        const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision);
+        const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule);
         if (device < 0)
           cpu_stencil(spec, a);
         else
@@ -352,7 +355,7 @@ PYBIND11_MODULE(_mdfx, m) {
       py::arg("lz_begin"), py::arg("lz_end"), py::arg("device"), py::arg("stream") = 0,
       py::arg("resid_ptr") = 0, py::arg("r") = -1.0, py::arg("c0") = 0.25, py::arg("c1") = 0.05,
       py::arg("c2") = 0.025, py::arg("c3") = 3.0 / 160.0, py::arg("steps") = 1, py::arg("ref_precision") = false,
-      py::arg("lz2_begin") = 0, py::arg("lz2_end") = 0);
+      py::arg("lz2_begin") = 0, py::arg("lz2_end") = 0, py::arg("rule") = "B3/S23");
   m.def(
       "init_field",
       [](const std::string& kind, const std::string& dtype, uintptr_t buf, int64_t nx, int64_t ny,
@@ -371,15 +374,16 @@ PYBIND11_MODULE(_mdfx, m) {
       py::arg("value") = 0.0, py::arg("edge") = 100.0, py::arg("interior") = 0.0,
       py::arg("density") = 0.15);
   m.def("hip_supports_steps", [](const std::string& kind, const std::string& dtype, int64_t nx, int64_t ny,
-                                 int64_t nz, int halo, int steps, bool ref_precision) {
-    StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision);
+                                 int64_t nz, int halo, int steps, bool ref_precision, const std::string& rule) {
+    StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision, rule);
     return hip_supports_steps(s, FieldLayout::make(Extent3{nx, ny, nz}, 0, nz, halo, dtype_from_name(dtype)), steps);
   }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("halo"),
-     py::arg("steps"), py::arg("ref_precision") = false);
-  m.def("hip_fused_depth", [](const std::string& kind, const std::string& dtype, int64_t nx, bool ref_precision) {
-    StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision);
+     py::arg("steps"), py::arg("ref_precision") = false, py::arg("rule") = "B3/S23");
+  m.def("hip_fused_depth", [](const std::string& kind, const std::string& dtype, int64_t nx, bool ref_precision,
+                              const std::string& rule) {
+    StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision, rule);
     return hip_fused_depth(s, nx);
-  }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ref_precision") = false);
+  }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ref_precision") = false, py::arg("rule") = "B3/S23");
   m.def("plan_sweeps", [](int64_t steps, int64_t start, int64_t residual_every, int temporal,
                           std::vector<double> cost, std::vector<bool> ok) {
     SweepCosts c;
@@ -401,15 +405,24 @@ PYBIND11_MODULE(_mdfx, m) {
   }, py::arg("residual_every"), py::arg("temporal"), py::arg("cost"), py::arg("ok"), py::arg("uniform") = false,
      "the deepest depth <= temporal that one residual interval's sweep plan runs (interval_depth)");
   m.def("hip_auto_depth", [](const std::string& kind, const std::string& dtype, int64_t nx, int64_t ny, int64_t nz,
-                             int want, int64_t residual_every, bool ref_precision, int nranks) {
-    StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision);
+                             int want, int64_t residual_every, bool ref_precision, int nranks,
+                             const std::string& rule) {
+    StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision, rule);
     return hip_interval_depth(s, Extent3{nx, ny, nz}, want, residual_every, nranks);
   }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("want"),
-     py::arg("residual_every"), py::arg("ref_precision") = false, py::arg("nranks") = 1,
+     py::arg("residual_every"), py::arg("ref_precision") = false, py::arg("nranks") = 1, py::arg("rule") = "B3/S23",
      "want, made shallower until one residual interval's plan runs a sweep of that depth (HIP cost tables)");
-  m.def("hip_sweep_cost", [](const std::string& kind, const std::string& dtype, int64_t nx, int steps) {
-    return hip_sweep_cost(make_spec(kind, dtype, -1, 0, 0, 0, 0, false), nx, steps);
-  }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("steps"));
+  m.def("hip_sweep_cost", [](const std::string& kind, const std::string& dtype, int64_t nx, int steps,
+                             const std::string& rule) {
+    return hip_sweep_cost(make_spec(kind, dtype, -1, 0, 0, 0, 0, false, rule), nx, steps);
+  }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("steps"), py::arg("rule") = "B3/S23");
+  m.def("life_rule_parse", [](const std::string& text) {
+    uint32_t b = 0, s = 0;
+    life_rule_from_name(text, b, s);
+    return std::make_pair(b, s);
+  }, py::arg("text"), "(birth, survive) masks of a Life-like rule in B/S notation (life_rule_from_name)");
+  m.def("life_rule_format", &life_rule_name, py::arg("birth"), py::arg("survive"),
+        "the canonical B/S text of two 9-bit masks (life_rule_name)");
   m.def("life_compat_init", [](int64_t h, int64_t w, double density, unsigned seed) {
     py::array_t<uint8_t> a({h, w});
     cpu_life_compat_init(a.mutable_data(), h, w, density, seed);
@@ -419,7 +432,8 @@ PYBIND11_MODULE(_mdfx, m) {
   py::class_<PySolver>(m, "Solver")
       .def(py::init<const std::string&, const std::string&, int64_t, int64_t, int64_t, int,
                     std::vector<int>, std::vector<int>, const std::string&, py::bytes, py::object,
-                    bool, bool, int, bool, double, double, double, double, double, double, int, bool, int, bool>(),
+                    bool, bool, int, bool, double, double, double, double, double, double, int, bool, int, bool,
+                    const std::string&>(),
            py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
            py::arg("nranks"), py::arg("local_ranks"), py::arg("devices"), py::arg("transport"),
            py::arg("unique_id") = py::bytes(""), py::arg("callbacks") = py::none(),
@@ -427,7 +441,7 @@ PYBIND11_MODULE(_mdfx, m) {
            py::arg("graph") = false, py::arg("timeout_s") = 0.0, py::arg("r") = -1.0,
            py::arg("c0") = 0.25, py::arg("c1") = 0.05, py::arg("c2") = 0.025,
            py::arg("c3") = 3.0 / 160.0, py::arg("temporal") = 1, py::arg("ref_precision") = false, py::arg("py") = 1,
-           py::arg("share_gpu") = false)
+           py::arg("share_gpu") = false, py::arg("rule") = "B3/S23")
       .def("close", &PySolver::close)
       .def("phase_times",
            [](PySolver& p) {

@@ -47,6 +47,8 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("--sync-debug", action="store_true")
     p.add_argument("--timeout", type=float, default=0.0)
     p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--rule", default="B3/S23",
+                   help="life: any Life-like rule in B/S notation, e.g. B36/S23, B3678/S34678, B2/S")
     p.add_argument("--resume", default="")
     p.add_argument("--dump", default="", help="write the final grid (checkpoint format) to this directory")
     p.add_argument("--print", action="store_true", help="print_array dump of the final grid (rank 0)")
@@ -66,6 +68,7 @@ def _problem(a):
             kw["dtype"] = a.dtype
         else:
             kw["seed"] = a.seed
+            kw["rule"] = a.rule
         return from_name(kind, **kw)
     n = a.n or 256
     return from_name(kind, nx=a.nx or n, ny=a.ny or n, nz=a.nz or n, dtype=a.dtype).with_init(seed=a.seed)

@@ -50,7 +50,8 @@ def auto_temporal(problem: Problem, nranks: int, device: str, py: int = 1, resid
         want = 4
         pz = nranks // py
         return want if problem.nz >= 4 * want * pz and problem.ny >= 4 * want * py else 1
-    want = native().hip_fused_depth(problem.kind, problem.dtype, problem.nx, problem.ref_precision)
+    want = native().hip_fused_depth(problem.kind, problem.dtype, problem.nx, problem.ref_precision,
+                                    rule=problem.rule)
     while want > 1 and problem.nz < 4 * want * nranks:
         want = {5: 4, 3: 2}.get(want, want // 2)
     if want > 1 and native().hip_supports_steps(problem.kind, problem.dtype, problem.nx, problem.ny, problem.nz,
@@ -58,7 +59,7 @@ def auto_temporal(problem: Problem, nranks: int, device: str, py: int = 1, resid
         # the depth for the residual interval (native interval_depth: least plan cost on one rank,
         # whole sweeps of the depth with several)
         return native().hip_auto_depth(problem.kind, problem.dtype, problem.nx, problem.ny, problem.nz, want,
-                                       residual_every, problem.ref_precision, nranks)
+                                       residual_every, problem.ref_precision, nranks, rule=problem.rule)
     return 1
 
 

@@ -6,7 +6,8 @@ the default initial condition. Families (reference parity in brackets):
 * :func:`mdf2d`   — 2D 5-point heat / Jacobi, Dirichlet edges = 100, interior 0
   [MDF_kernel.cu:10-22 update, :88-99 initial grid]
 * :func:`life2d`  — Conway's Game of Life, Moore-8, B3/S23, dead frame, density 0.15
-  [kernel.cu:10-68 update, :131-146 initial grid]
+  [kernel.cu:10-68 update, :131-146 initial grid]; ``rule="B36/S23"`` runs any other Life-like
+  (outer-totalistic) rule
 * :func:`heat3d`  — 3D 7-point heat / Jacobi (headline benchmark, BASELINE.json configs 2, 3, 5)
 * :func:`box27`   — 3D 27-point weighted stencil (BASELINE.json config 4)
 * :func:`box9`    — 2D 9-point weighted stencil (centre, edge and corner weights), Dirichlet edges
@@ -51,6 +52,9 @@ class Problem:
     # 2D MDF: evaluate the update exactly as the reference does (fp32 sum, fp64 scale and add;
     # MDF_kernel.cu:20) instead of wholly in the field type; single-step sweeps only
     ref_precision: bool = False
+    # Life only: the rule in B/S notation (digits = neighbour counts that give birth / let a cell
+    # survive), any of the 2^18 outer-totalistic Moore rules; parsed by the native core
+    rule: str = "B3/S23"
     init: InitCondition = field(default_factory=InitCondition)
 
     def __post_init__(self):
@@ -62,6 +66,15 @@ class Problem:
             raise ValueError("life cells are u8")
         if self.kind != "life" and self.dtype not in ("f32", "f64"):
             raise ValueError("stencil dtype must be f32 or f64")
+        if self.rule != "B3/S23":
+            if self.kind != "life":
+                raise ValueError("rule applies to kind 'life' only")
+            from .._native import native
+
+            try:
+                native().life_rule_parse(self.rule)
+            except RuntimeError as e:
+                raise ValueError(str(e)) from None
         for n in (self.nx, self.ny, self.nz):
             if n < 1:
                 raise ValueError("grid extents must be positive")
@@ -89,11 +102,23 @@ class Problem:
         return replace(self, init=replace(self.init, **kw))
 
     def coef_kwargs(self) -> dict:
-        return dict(r=self.r, c0=self.c0, c1=self.c1, c2=self.c2, c3=self.c3, ref_precision=self.ref_precision)
+        return dict(r=self.r, c0=self.c0, c1=self.c1, c2=self.c2, c3=self.c3, ref_precision=self.ref_precision,
+                    rule=self.rule)
+
+    @property
+    def conway(self) -> bool:
+        return self.kind != "life" or native_rule(self.rule) == (0x008, 0x00C)
 
     def describe(self) -> str:
         shape = "%dx%d" % (self.nz, self.nx) if self.dims == 2 else "%dx%dx%d" % (self.nx, self.ny, self.nz)
-        return "%s %s %s" % (self.kind, shape, self.dtype)
+        return "%s %s %s" % (self.kind, shape, self.dtype) + ("" if self.conway else " " + self.rule)
+
+
+def native_rule(rule: str) -> tuple:
+    """(birth, survive) 9-bit masks of a rule text, through the native parser."""
+    from .._native import native
+
+    return tuple(native().life_rule_parse(rule))
 
 
 def mdf2d(h: int = 256, w: int = 256, dtype: str = "f32", r: float = 0.25,
@@ -105,9 +130,10 @@ def mdf2d(h: int = 256, w: int = 256, dtype: str = "f32", r: float = 0.25,
 
 
 def life2d(h: int = 256, w: int = 256, density: float = 0.15, seed: int = 1,
-           init: Optional[InitCondition] = None) -> Problem:
-    """Conway's Game of Life on an h x w board with a dead frame."""
-    return Problem("life", nx=w, ny=1, nz=h, dtype="u8",
+           init: Optional[InitCondition] = None, rule: str = "B3/S23") -> Problem:
+    """Game of Life on an h x w board with a dead frame: Conway's rule, or any Life-like ``rule``
+    (HighLife "B36/S23", Day & Night "B3678/S34678", Seeds "B2/S", ...)."""
+    return Problem("life", nx=w, ny=1, nz=h, dtype="u8", rule=rule,
                    init=init or InitCondition(kind="life", density=density, seed=seed))
 
 

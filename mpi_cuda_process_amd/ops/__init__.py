@@ -155,7 +155,8 @@ def advance(problem: Problem, grid: torch.Tensor, steps: int, temporal: int = 0)
                          (tuple(grid.shape), problem.nz, problem.ny, problem.nx))
     dev = g.device
     if temporal <= 0:
-        want = native().hip_fused_depth(problem.kind, problem.dtype, problem.nx, problem.ref_precision)
+        want = native().hip_fused_depth(problem.kind, problem.dtype, problem.nx, problem.ref_precision,
+                                        rule=problem.rule)
         while want > 1 and problem.nz < want:
             want = 2 if want == 3 else want // 2
         temporal = 1

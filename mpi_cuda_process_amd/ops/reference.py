@@ -68,8 +68,13 @@ def box9(u: torch.Tensor, c0: float = 1.0 / 3.0, c1: float = 2.0 / 15.0, c2: flo
     return out if squeeze else out.unsqueeze(1)
 
 
-def life(u: torch.Tensor) -> torch.Tensor:
-    """Game of Life B3/S23 with a held (dead) frame; ``u`` is (h, 1, w) or (h, w) uint8."""
+def life(u: torch.Tensor, rule: str = "B3/S23") -> torch.Tensor:
+    """Game of Life with a held (dead) frame, Conway's B3/S23 or any Life-like ``rule``; ``u`` is
+    (h, 1, w) or (h, w) uint8. Integer arithmetic: the neighbour count, then a lookup in the rule's
+    two 9-bit masks."""
+    from ..models import native_rule
+
+    birth, survive = native_rule(rule)
     squeeze = u.dim() == 2
     g = (u if squeeze else u[:, 0, :]).to(torch.int32)
     out = g.clone()
@@ -82,7 +87,8 @@ def life(u: torch.Tensor) -> torch.Tensor:
                     continue
                 n += g[1 + dz:h - 1 + dz, 1 + dx:w - 1 + dx]
         alive = g[1:-1, 1:-1]
-        out[1:-1, 1:-1] = ((n == 3) | ((n == 2) & (alive == 1))).to(torch.int32)
+        table = torch.where(alive == 1, torch.full_like(n, survive), torch.full_like(n, birth))
+        out[1:-1, 1:-1] = (table >> n) & 1
     out = out.to(torch.uint8)
     return out if squeeze else out.unsqueeze(1)
 
@@ -100,7 +106,7 @@ def step(kind: str, u: torch.Tensor, **coef) -> torch.Tensor:
     if kind == "box9":
         return box9(u, coef.get("c0", 1.0 / 3.0), coef.get("c1", 2.0 / 15.0), coef.get("c2", 1.0 / 30.0))
     if kind == "life":
-        return life(u)
+        return life(u, coef.get("rule", "B3/S23"))
     raise ValueError(kind)
 
 
