@@ -40,6 +40,7 @@ struct Opts {
   bool compat = false;
   bool ref_precision = false;
   std::string rule;  // --rule B36/S23 (Life); empty = Conway's B3/S23
+  std::string weights;  // --weights c0,xm,xp,ym,yp,zm,zp (star7); empty = the defaults
   int temporal = 0;  // 0 = auto: hip_fused_depth on HIP where a fused kernel exists, else 1
   int py = 1;        // --py: ranks along y of a (z, y) pencil split
   bool profile = false;
@@ -51,8 +52,9 @@ void usage(const char* prog) {
   std::printf(
       "usage: %s [options]\n"
       "  With no size/step options the reference dialogue runs on stdin (generations, height, width).\n"
-      "  --stencil 5|7|9|27|life   stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
-      "                            9 = 2D 9-pt with --c0 --c1 --c2, default 1/3, 2/15, 1/30)\n"
+      "  --stencil 5|7|9|27|star7|life  stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
+      "                            9 = 2D 9-pt with --c0 --c1 --c2, default 1/3, 2/15, 1/30; star7 = 3D\n"
+      "                            7-pt with seven weights, see --weights)\n"
       "  --n N | --nx --ny --nz    3D grid (N^3) ; 2D: --h ROWS --w COLS\n"
       "  --steps K (--iters, -g)   time steps / generations ; --warmup W untimed steps first\n"
       "  --dtype f32|f64           element type (life is always u8)\n"
@@ -67,6 +69,8 @@ void usage(const char* prog) {
       "                            default - ipc yes, rccl no)\n"
       "  --init random|dirichlet|constant|life|compat  --seed --lo --hi --value --edge --interior --density\n"
       "  --r R | --c0 --c1 --c2 --c3   update coefficients\n"
+      "  --weights c0,xm,xp,ym,yp,zm,zp  star7: the centre weight and the weights of u(x-1), u(x+1), u(y-1),\n"
+      "                            u(y+1), u(z-1), u(z+1); default 0.3,0.2,0.2,0.1,0.1,0.05,0.05\n"
       "  --ref-precision           2D MDF: the reference's fp32-sum / fp64-scale evaluation of the update\n"
       "                            (default in the reference dialogue; single-step sweeps)\n"
       "  --rule B<n..>/S<n..>      Life: any outer-totalistic Moore rule, e.g. B36/S23 (HighLife),\n"
@@ -149,6 +153,7 @@ Opts parse(int argc, char** argv, const char* prog) {
     else if (a == "--compat") o.compat = true;
     else if (a == "--ref-precision") o.ref_precision = true;
     else if (a == "--rule") o.rule = need(i);
+    else if (a == "--weights") o.weights = need(i);
     else if (a == "--temporal") o.temporal = std::atoi(need(i));
     else if (a == "--py") o.py = std::atoi(need(i));
     else if (a == "--profile") o.profile = true;
@@ -254,12 +259,16 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     spec.coef.r = o.r;
     // weights not given: the 27-point's 1/4, 1/20, 1/40; the 9-point's 1/3, 2/15, 1/30
     const bool b9 = kind == StencilKind::Box9;
-    spec.coef.c0 = !std::isnan(o.c0) ? o.c0 : (b9 ? 1.0 / 3.0 : 0.25);
+    spec.coef.c0 = !std::isnan(o.c0) ? o.c0 : (b9 ? 1.0 / 3.0 : kind == StencilKind::Star7 ? kStar7C0 : 0.25);
     spec.coef.c1 = !std::isnan(o.c1) ? o.c1 : (b9 ? 2.0 / 15.0 : 0.05);
     spec.coef.c2 = !std::isnan(o.c2) ? o.c2 : (b9 ? 1.0 / 30.0 : 0.025);
     spec.coef.c3 = o.c3;
     // the reference dialogue reproduces the reference's arithmetic too (MDF_kernel.cu:20, D17)
     spec.coef.ref_precision = kind == StencilKind::Jacobi5 && (o.ref_precision || o.compat);
+    if (!o.weights.empty()) {
+      MDFX_CHECK(kind == StencilKind::Star7, "--weights goes with --stencil star7");
+      star7_weights_from_text(o.weights, spec.coef);
+    }
     if (!o.rule.empty()) {
       MDFX_CHECK(kind == StencilKind::Life, "--rule goes with --stencil life");
       life_rule_from_name(o.rule, spec.coef.birth, spec.coef.survive);

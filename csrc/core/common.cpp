@@ -1,4 +1,5 @@
 // mdfx core: error helpers, enum names, layout and slab decomposition math.
+#include <algorithm>
 #include <csignal>
 #include <cstdarg>
 #include <cstdlib>
@@ -79,6 +80,7 @@ const char* stencil_name(StencilKind k) {
     case StencilKind::Heat7: return "heat7";
     case StencilKind::Box27: return "box27";
     case StencilKind::Box9: return "box9";
+    case StencilKind::Star7: return "star7";
   }
   return "?";
 }
@@ -89,7 +91,8 @@ StencilKind stencil_from_name(const std::string& s) {
   if (s == "heat7" || s == "7" || s == "jacobi7" || s == "7pt") return StencilKind::Heat7;
   if (s == "box27" || s == "27" || s == "27pt") return StencilKind::Box27;
   if (s == "box9" || s == "9" || s == "9pt") return StencilKind::Box9;
-  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|life)");
+  if (s == "star7" || s == "s7") return StencilKind::Star7;
+  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|star7|life)");
 }
 
 void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive) {
@@ -117,6 +120,37 @@ std::string life_rule_name(uint32_t birth, uint32_t survive) {
   for (int n = 0; n <= 8; ++n)
     if (survive >> n & 1u) s += (char)('0' + n);
   return s;
+}
+
+void star7_check_weights(const StencilCoef& c) {
+  const double w[7] = {c.c0, c.wxm, c.wxp, c.wym, c.wyp, c.wzm, c.wzp};
+  for (double v : w)
+    if (!std::isfinite(v)) MDFX_FAIL("star7 weights must be finite (c0, xm, xp, ym, yp, zm, zp)");
+}
+
+void star7_weights_from_text(const std::string& s, StencilCoef& coef) {
+  double w[7];
+  int n = 0;
+  size_t pos = 0;
+  bool ok = !s.empty();
+  while (ok && pos <= s.size()) {
+    const size_t end = std::min(s.find(',', pos), s.size());
+    const std::string part = s.substr(pos, end - pos);
+    char* tail = nullptr;
+    const double v = std::strtod(part.c_str(), &tail);
+    ok = !part.empty() && tail && *tail == '\0' && std::isfinite(v) && n < 7;
+    if (ok) w[n++] = v;
+    pos = end + 1;
+  }
+  if (!ok || n != 7)
+    MDFX_FAIL("star7 weights '" + s + "': expected seven comma-separated finite numbers c0,xm,xp,ym,yp,zm,zp");
+  coef.c0 = w[0];
+  coef.wxm = w[1];
+  coef.wxp = w[2];
+  coef.wym = w[3];
+  coef.wyp = w[4];
+  coef.wzm = w[5];
+  coef.wzp = w[6];
 }
 
 FieldLayout FieldLayout::make(Extent3 g, int64_t z0, int64_t z1, int halo, DType dt, int64_t y0, int64_t y1, int hy) {

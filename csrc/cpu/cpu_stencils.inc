@@ -159,6 +159,35 @@ void box9_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const St
   if (RES) *resid += acc;
 }
 
+// 3D 7-point star with seven weights: sm::star7, the chain the device kernels evaluate
+template <class T, bool RES>
+void star7_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const StencilCoef& cf, double* resid) {
+  const sm::Star7W<T> w{(T)cf.c0, (T)cf.wxm, (T)cf.wxp, (T)cf.wym, (T)cf.wyp, (T)cf.wzm, (T)cf.wzp};
+  double acc = 0.0;
+#pragma omp parallel for schedule(static) reduction(+ : acc) if ((le - lb) * (g.ye - g.yb) * g.nx > 262144)
+  for (int64_t lz = lb; lz < le; ++lz) {
+    const int64_t gz = lz + g.gz_off;
+    for (int64_t y = g.yb; y < g.ye; ++y) {
+      const int64_t row = lz * g.plane + y * g.pitch;
+      const T* __restrict__ c = in + row;
+      T* __restrict__ o = out + row;
+      const int64_t gy = y + g.gy_off;
+      if (gz > 0 && gz < g.gnz - 1 && gy > 0 && gy < g.gny - 1 && g.nx > 2) {
+        const T *__restrict__ ym = c - g.pitch, *__restrict__ yp = c + g.pitch;
+        const T *__restrict__ zm = c - g.plane, *__restrict__ zp = c + g.plane;
+        o[0] = c[0];
+#pragma omp simd
+        for (int64_t x = 1; x < g.nx - 1; ++x) o[x] = sm::star7<T>(c[x], c[x - 1], c[x + 1], ym[x], yp[x], zm[x], zp[x], w);
+        o[g.nx - 1] = c[g.nx - 1];
+      } else {
+        std::memcpy(o, c, (size_t)g.nx * sizeof(T));
+      }
+      if (RES) acc += row_resid(o, c, g.nx);
+    }
+  }
+  if (RES) *resid += acc;
+}
+
 // CONWAY: sm::life_rule (B3/S23); otherwise sm::life_like with the spec's two masks
 template <bool RES, bool CONWAY>
 void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t le, unsigned birth, unsigned survive,
@@ -224,6 +253,12 @@ void region_t(const StencilSpec& spec, const RegionArgs& a) {
         box9_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       else
         box9_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      break;
+    case StencilKind::Star7:
+      if (spec.dtype == DType::F32)
+        star7_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      else
+        star7_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       break;
     case StencilKind::Life:
       if (spec.conway())

@@ -51,6 +51,7 @@ enum class StencilKind : int {
   Heat7 = 2,    // 3D 7-point heat / Jacobi (BASELINE.json configs 2, 3, 5)
   Box27 = 3,    // 3D 27-point weighted stencil (BASELINE.json config 4)
   Box9 = 4,     // 2D 9-point weighted stencil (centre, edge and corner weights)
+  Star7 = 5,    // 3D 7-point star with seven independent weights (anisotropy, advection, decay)
 };
 const char* stencil_name(StencilKind k);
 StencilKind stencil_from_name(const std::string& s);
@@ -60,10 +61,15 @@ inline bool stencil_is_2d(StencilKind k) {
 
 // Coefficients. Jacobi5/Heat7: u' = u + r * (sum_neighbours - 2d * u). Box27:
 // u' = c0*u + c1*sum(6 faces) + c2*sum(12 edges) + c3*sum(8 corners). Box9:
-// u' = c0*u + c1*sum(4 edges) + c2*sum(4 corners) (c3 unused).
+// u' = c0*u + c1*sum(4 edges) + c2*sum(4 corners) (c3 unused). Star7:
+// u' = c0*u + wxm*u(x-1) + wxp*u(x+1) + wym*u(y-1) + wyp*u(y+1) + wzm*u(z-1) + wzp*u(z+1), evaluated as
+// sm::star7; its default c0 is kStar7C0 (c0 is shared with the box families, whose default is 0.25).
+// Sum |w| <= 1 keeps the max-norm from growing.
+constexpr double kStar7C0 = 0.30;
 struct StencilCoef {
   double r = -1.0;  // < 0 -> default 1/(2d) (Jacobi)
   double c0 = 0.25, c1 = 1.0 / 20.0, c2 = 1.0 / 40.0, c3 = 3.0 / 160.0;
+  double wxm = 0.20, wxp = 0.20, wym = 0.10, wyp = 0.10, wzm = 0.05, wzp = 0.05;  // Star7 neighbour weights
   // 2D MDF only: evaluate the update exactly as the reference does (sm::jacobi5_ref: fp32 sum and
   // -4u, fp64 scale and add, one more rounding at the store) instead of wholly in the field type.
   // See StencilSpec::mixed_update() for when the two can differ at all.
@@ -78,6 +84,11 @@ struct StencilCoef {
 // side may be empty ("B2/S"). Anything else throws an Error that names the text.
 void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive);
 std::string life_rule_name(uint32_t birth, uint32_t survive);  // canonical form, digits ascending
+
+// Star7 weights as text: "c0,xm,xp,ym,yp,zm,zp", seven comma-separated finite numbers. Any other count,
+// a non-number or a non-finite value throws an Error that names the text.
+void star7_weights_from_text(const std::string& s, StencilCoef& coef);
+void star7_check_weights(const StencilCoef& coef);  // every Star7 weight finite, else an Error
 
 struct StencilSpec {
   StencilKind kind = StencilKind::Heat7;

@@ -87,6 +87,34 @@ MDFX_HDI T box9_combine(T a_m, T b_c, T a_p) {
   return (a_m + b_c) + a_p;
 }
 
+// 3D 7-point star with seven independent weights (star7): a pure chain of one multiply and six fmas,
+// ordered for a march along z. For one cell,
+//   B  = fma(wyp, yp, fma(wym, ym, fma(wxp, xp, fma(wxm, xm, c0 * c))))   the cell's own plane
+//   P  = fma(wzm, zm, B)        complete once plane z has arrived
+//   u' = fma(wzp, zp, P)        finished when plane z + 1 arrives
+// wxm multiplies u(x-1), wxp multiplies u(x+1); y and z alike.
+template <class T>
+struct Star7W {
+  T c0, xm, xp, ym, yp, zm, zp;
+};
+template <class T>
+MDFX_HDI T star7_B(T c, T xm, T xp, T ym, T yp, T k0, T kxm, T kxp, T kym, T kyp) {
+  return fmaT(kyp, yp, fmaT(kym, ym, fmaT(kxp, xp, fmaT(kxm, xm, k0 * c))));
+}
+template <class T>
+MDFX_HDI T star7_P(T B, T zm, T kzm) {
+  return fmaT(kzm, zm, B);
+}
+template <class T>
+MDFX_HDI T star7_finish(T P, T zp, T kzp) {
+  return fmaT(kzp, zp, P);
+}
+template <class T>
+MDFX_HDI T star7(T c, T xm, T xp, T ym, T yp, T zm, T zp, const Star7W<T>& w) {
+  const T B = star7_B<T>(c, xm, xp, ym, yp, w.c0, w.xm, w.xp, w.ym, w.yp);
+  return star7_finish<T>(star7_P<T>(B, zm, w.zm), zp, w.zp);
+}
+
 // Life: T = sum of the 3x3 block including self.
 MDFX_HDI unsigned char life_rule(unsigned t, unsigned char alive) {
   return (unsigned char)((t == 3u) | ((t == 4u) & (alive != 0)));

@@ -39,6 +39,9 @@ void launch_box27(const Geo& g, const T* in, T* out, const StencilCoef& c, doubl
 // 2D 9-point: box9_wave (steps = 1) and box9_tbk (2, 3, 4, 6, 8 fused steps), stencil_box9.hip
 template <class T>
 void launch_box9(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
+// 3D 7-point star with seven weights: star7_tbk (1, 2, 3, 4 steps per sweep), stencil_star7.hip
+template <class T>
+void launch_star7(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
 void launch_life(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tb2(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tbk(const Geo& g, const uint8_t* in, uint8_t* out, int steps, double* resid, hipStream_t s);
@@ -261,6 +264,7 @@ bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int ste
   if (spec.kind == StencilKind::Jacobi5)  // deep temporal blocking of the 2D problems
     return (spec.dtype == DType::F32 || spec.dtype == DType::F64) && k2d;  // ref precision too (jacobi5_tbk REF)
   if (spec.kind == StencilKind::Box9) return k2d;  // box9_tbk
+  if (spec.kind == StencilKind::Star7) return steps <= 4;  // star7_tbk: any nx, ny, nz
   // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
   if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;
   if (spec.kind == StencilKind::Heat7 && steps > 2) {  // deep temporal blocking (rows within one block)
@@ -295,6 +299,12 @@ int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
       // 1123 / 1706 / 2277 / 3400 / 4611), fp64 281 / 564 / 835 / 1104 / 1759 / 1901 (304 / 613 / 904 /
       // 1203 / 1639 / 2276); the sweeps stay at the memory roof up to K = 6 (profiles/r07_box9/)
       return 8;
+    case StencilKind::Star7:
+      // K = 3 is the fastest per step for both dtypes: 512^3 fp32 565 / 879 / 995 / 666 GCells/s for
+      // K = 1 / 2 / 3 / 4 (heat7's kernels in the same call: 669 / 1300 / 1650 / 2031), fp64 294 / 473 /
+      // 552 / 266 (322 / 618 / 731 / 1011). star7_tbk's strips are 4 / 4 / 3 (fp64 2) / 1 rows (deeper
+      // strips spilled), so K = 4 updates 2.5 rows per row it stores (profiles/r09_star7/)
+      return 3;
     case StencilKind::Life:
       // any other rule (life_rule_bits): 12 as well, by its own measurement. 32768^2, HighLife, GCells/s
       // for K = 1 / 2 / 3 / 4 / 6 / 8 / 12 / 16: 2232 / 4415 / 6532 / 8584 / 12656 / 16217 / 19233 / 16380
@@ -365,6 +375,13 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
     static const double f64[9] = {0.0, 1.0, 1.00, 1.01, 1.02, 0.0, 0.96, 0.0, 1.18};
     const double c = (spec.dtype == DType::F64 ? f64 : f32)[steps];
     if (c > 0.0) return c;
+  }
+  if (spec.kind == StencilKind::Star7 && steps <= 4) {
+    // star7_tbk's per-sweep times against its single step at 512^3 (profiles/r09_star7/): the trapezoid's
+    // redundant rows make every fused sweep cost more than one pass, and K = 4 more than two sweeps of 2
+    static const double f32[5] = {0.0, 1.0, 1.29, 1.70, 3.39};
+    static const double f64[5] = {0.0, 1.0, 1.24, 1.60, 4.41};
+    return (spec.dtype == DType::F64 ? f64 : f32)[steps];
   }
   if (spec.kind == StencilKind::Life && !spec.conway() && steps <= 16 && nx >= 8192) {
     // life_rule_bits' per-sweep times against its own single step at 32768^2 (profiles/r08_life_rules/):
@@ -455,6 +472,11 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
         dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
       else
         dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
+    } else if (spec.kind == StencilKind::Star7) {
+      if (spec.dtype == DType::F32)
+        dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
+      else
+        dev::launch_star7<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
     } else if (spec.kind == StencilKind::Life && !spec.conway()) {
       dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, a.steps,
                             a.resid, s);
@@ -534,6 +556,12 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
           dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
         else
           dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
+        break;
+      case StencilKind::Star7:
+        if (spec.dtype == DType::F32)
+          dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
+        else
+          dev::launch_star7<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
         break;
       case StencilKind::Life:
         if (spec.conway())

@@ -148,6 +148,8 @@ __global__ __launch_bounds__(256) void naive_life(const uint8_t* __restrict__ in
 
 template <class T>
 void launch_box9_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
+template <class T>
+void launch_star7_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
 
 static int naive_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
@@ -193,6 +195,12 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
         launch_box9_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
       else
         launch_box9_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
+      break;
+    case StencilKind::Star7:  // (the kernel lives in stencil_star7.hip, built without packed fp32 ops)
+      if (spec.dtype == DType::F32)
+        launch_star7_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
+      else
+        launch_star7_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
       break;
     case StencilKind::Life: {
       const TableRule tr{spec.coef.birth, spec.coef.survive};

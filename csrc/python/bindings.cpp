@@ -80,7 +80,8 @@ py::capsule make_dlpack(void* data, int device, DType dt, std::vector<int64_t> s
 
 StencilSpec make_spec(const std::string& kind, const std::string& dtype, double r, double c0,
                       double c1, double c2, double c3, bool ref_precision = false,
-                      const std::string& rule = "B3/S23") {
+                      const std::string& rule = "B3/S23", double wxm = 0.20, double wxp = 0.20, double wym = 0.10,
+                      double wyp = 0.10, double wzm = 0.05, double wzp = 0.05) {
   StencilSpec s;
   s.coef.ref_precision = ref_precision;
   life_rule_from_name(rule, s.coef.birth, s.coef.survive);
@@ -91,6 +92,13 @@ StencilSpec make_spec(const std::string& kind, const std::string& dtype, double 
   s.coef.c1 = c1;
   s.coef.c2 = c2;
   s.coef.c3 = c3;
+  s.coef.wxm = wxm;
+  s.coef.wxp = wxp;
+  s.coef.wym = wym;
+  s.coef.wyp = wyp;
+  s.coef.wzm = wzm;
+  s.coef.wzp = wzp;
+  if (s.kind == StencilKind::Star7) star7_check_weights(s.coef);
   return s;
 }
 
@@ -209,8 +217,8 @@ class PySolver {
            const std::string& transport, py::bytes unique_id, py::object callbacks, bool overlap,
            bool sync_debug, int residual_every, bool graph, double timeout_s, double r, double c0,
            double c1, double c2, double c3, int temporal, bool ref_precision, int pencil_py, bool share_gpu,
-           const std::string& rule) {
-    const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule);
+           const std::string& rule, double wxm, double wxp, double wym, double wyp, double wzm, double wzp) {
+    const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule, wxm, wxp, wym, wyp, wzm, wzp);
     if (devices.size() == 1 && local_ranks.size() > 1) devices.assign(local_ranks.size(), devices[0]);
     if (devices.size() != local_ranks.size())
       throw Error("devices must have one entry per local rank (or a single entry)");
@@ -333,7 +341,8 @@ PYBIND11_MODULE(_mdfx, m) {
       [](const std::string& kind, const std::string& dtype, uintptr_t in, uintptr_t out, int64_t nx,
          int64_t ny, int64_t nz, int64_t z0, int64_t z1, int halo, int64_t lz_begin, int64_t lz_end,
          int device, uintptr_t stream, uintptr_t resid, double r, double c0, double c1, double c2,
-         double c3, int steps, bool ref_precision, int64_t lz2_begin, int64_t lz2_end, const std::string& rule) {
+         double c3, int steps, bool ref_precision, int64_t lz2_begin, int64_t lz2_end, const std::string& rule,
+         double wxm, double wxp, double wym, double wyp, double wzm, double wzp) {
         RegionArgs a;
         a.lz2_begin = lz2_begin;
         a.lz2_end = lz2_end;
@@ -344,7 +353,7 @@ PYBIND11_MODULE(_mdfx, m) {
         a.lz_end = lz_end;
         a.resid = (double*)resid;
         a.steps = steps;
-        const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule);
+        const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule, wxm, wxp, wym, wyp, wzm, wzp);
         if (device < 0)
           cpu_stencil(spec, a);
         else
@@ -355,7 +364,8 @@ PYBIND11_MODULE(_mdfx, m) {
       py::arg("lz_begin"), py::arg("lz_end"), py::arg("device"), py::arg("stream") = 0,
       py::arg("resid_ptr") = 0, py::arg("r") = -1.0, py::arg("c0") = 0.25, py::arg("c1") = 0.05,
       py::arg("c2") = 0.025, py::arg("c3") = 3.0 / 160.0, py::arg("steps") = 1, py::arg("ref_precision") = false,
-      py::arg("lz2_begin") = 0, py::arg("lz2_end") = 0, py::arg("rule") = "B3/S23");
+      py::arg("lz2_begin") = 0, py::arg("lz2_end") = 0, py::arg("rule") = "B3/S23", py::arg("wxm") = 0.20, py::arg("wxp") = 0.20,
+      py::arg("wym") = 0.10, py::arg("wyp") = 0.10, py::arg("wzm") = 0.05, py::arg("wzp") = 0.05);
   m.def(
       "init_field",
       [](const std::string& kind, const std::string& dtype, uintptr_t buf, int64_t nx, int64_t ny,
@@ -433,7 +443,7 @@ PYBIND11_MODULE(_mdfx, m) {
       .def(py::init<const std::string&, const std::string&, int64_t, int64_t, int64_t, int,
                     std::vector<int>, std::vector<int>, const std::string&, py::bytes, py::object,
                     bool, bool, int, bool, double, double, double, double, double, double, int, bool, int, bool,
-                    const std::string&>(),
+                    const std::string&, double, double, double, double, double, double>(),
            py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
            py::arg("nranks"), py::arg("local_ranks"), py::arg("devices"), py::arg("transport"),
            py::arg("unique_id") = py::bytes(""), py::arg("callbacks") = py::none(),
@@ -441,7 +451,8 @@ PYBIND11_MODULE(_mdfx, m) {
            py::arg("graph") = false, py::arg("timeout_s") = 0.0, py::arg("r") = -1.0,
            py::arg("c0") = 0.25, py::arg("c1") = 0.05, py::arg("c2") = 0.025,
            py::arg("c3") = 3.0 / 160.0, py::arg("temporal") = 1, py::arg("ref_precision") = false, py::arg("py") = 1,
-           py::arg("share_gpu") = false, py::arg("rule") = "B3/S23")
+           py::arg("share_gpu") = false, py::arg("rule") = "B3/S23", py::arg("wxm") = 0.20, py::arg("wxp") = 0.20,
+           py::arg("wym") = 0.10, py::arg("wyp") = 0.10, py::arg("wzm") = 0.05, py::arg("wzp") = 0.05)
       .def("close", &PySolver::close)
       .def("phase_times",
            [](PySolver& p) {

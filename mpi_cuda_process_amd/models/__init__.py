@@ -11,6 +11,8 @@ the default initial condition. Families (reference parity in brackets):
 * :func:`heat3d`  — 3D 7-point heat / Jacobi (headline benchmark, BASELINE.json configs 2, 3, 5)
 * :func:`box27`   — 3D 27-point weighted stencil (BASELINE.json config 4)
 * :func:`box9`    — 2D 9-point weighted stencil (centre, edge and corner weights), Dirichlet edges
+* :func:`star7`   — 3D 7-point star with seven independent weights (anisotropic grids and conductivities,
+  constant-velocity advection-diffusion, decay), Dirichlet faces
 
 2D grids are stored as ``nx = w, ny = 1, nz = h``: rows are the slab axis, exactly like the
 reference's row split (MDF_kernel.cu:30,54).
@@ -21,7 +23,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field, replace
 from typing import Optional
 
-KINDS = ("jacobi5", "life", "heat7", "box27", "box9")
+KINDS = ("jacobi5", "life", "heat7", "box27", "box9", "star7")
 KINDS_2D = ("jacobi5", "life", "box9")
 
 
@@ -49,6 +51,13 @@ class Problem:
     c1: float = 1.0 / 20.0
     c2: float = 1.0 / 40.0
     c3: float = 3.0 / 160.0
+    # star7 only: the neighbour weights (wxm multiplies u(x-1), wxp multiplies u(x+1), ...); c0 is the centre
+    wxm: float = 0.20
+    wxp: float = 0.20
+    wym: float = 0.10
+    wyp: float = 0.10
+    wzm: float = 0.05
+    wzp: float = 0.05
     # 2D MDF: evaluate the update exactly as the reference does (fp32 sum, fp64 scale and add;
     # MDF_kernel.cu:20) instead of wholly in the field type; single-step sweeps only
     ref_precision: bool = False
@@ -103,7 +112,8 @@ class Problem:
 
     def coef_kwargs(self) -> dict:
         return dict(r=self.r, c0=self.c0, c1=self.c1, c2=self.c2, c3=self.c3, ref_precision=self.ref_precision,
-                    rule=self.rule)
+                    rule=self.rule, wxm=self.wxm, wxp=self.wxp, wym=self.wym, wyp=self.wyp, wzm=self.wzm,
+                    wzp=self.wzp)
 
     @property
     def conway(self) -> bool:
@@ -161,14 +171,26 @@ def box9(h: int = 256, w: int = 256, dtype: str = "f32", c0: float = 1.0 / 3.0, 
                    init=init or InitCondition(kind="dirichlet", edge=100.0, interior=0.0))
 
 
+def star7(n: int = 256, nx: Optional[int] = None, ny: Optional[int] = None, nz: Optional[int] = None,
+          dtype: str = "f32", c0: float = 0.30, wxm: float = 0.20, wxp: float = 0.20, wym: float = 0.10,
+          wyp: float = 0.10, wzm: float = 0.05, wzp: float = 0.05, init: Optional[InitCondition] = None) -> Problem:
+    """3D 7-point star u' = c0 u + wxm u(x-1) + wxp u(x+1) + wym u(y-1) + wyp u(y+1) + wzm u(z-1) +
+    wzp u(z+1) on an nx x ny x nz grid (default n^3), Dirichlet faces. The default is an anisotropic
+    diffusion whose weights sum to 1. Weights must be finite; sum |w| <= 1 keeps the max-norm from
+    growing."""
+    return Problem("star7", nx=nx or n, ny=ny or n, nz=nz or n, dtype=dtype, c0=c0, wxm=wxm, wxp=wxp, wym=wym,
+                   wyp=wyp, wzm=wzm, wzp=wzp, init=init or InitCondition(kind="random", seed=1))
+
+
 def from_name(kind: str, **kw) -> Problem:
     aliases = {"5": "jacobi5", "mdf": "jacobi5", "jacobi5": "jacobi5", "life": "life", "gol": "life",
                "7": "heat7", "heat7": "heat7", "jacobi7": "heat7", "27": "box27", "box27": "box27",
-               "9": "box9", "9pt": "box9", "box9": "box9"}
+               "9": "box9", "9pt": "box9", "box9": "box9", "star7": "star7", "s7": "star7"}
     k = aliases.get(str(kind))
     if k is None:
         raise ValueError("unknown stencil %r" % kind)
-    return {"jacobi5": mdf2d, "life": life2d, "heat7": heat3d, "box27": box27, "box9": box9}[k](**kw)
+    return {"jacobi5": mdf2d, "life": life2d, "heat7": heat3d, "box27": box27, "box9": box9,
+            "star7": star7}[k](**kw)
 
 
-__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "from_name", "KINDS"]
+__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "from_name", "KINDS"]

@@ -68,6 +68,18 @@ def box9(u: torch.Tensor, c0: float = 1.0 / 3.0, c1: float = 2.0 / 15.0, c2: flo
     return out if squeeze else out.unsqueeze(1)
 
 
+def star7(u: torch.Tensor, c0: float = 0.30, wxm: float = 0.20, wxp: float = 0.20, wym: float = 0.10,
+          wyp: float = 0.10, wzm: float = 0.05, wzp: float = 0.05) -> torch.Tensor:
+    """3D 7-point star with seven weights; ``u`` is (nz, ny, nx). wxm multiplies u(x-1), wxp u(x+1)."""
+    out = u.clone()
+    if min(u.shape) < 3:
+        return out
+    out[1:-1, 1:-1, 1:-1] = (c0 * u[1:-1, 1:-1, 1:-1] + wxm * u[1:-1, 1:-1, :-2] + wxp * u[1:-1, 1:-1, 2:]
+                             + wym * u[1:-1, :-2, 1:-1] + wyp * u[1:-1, 2:, 1:-1]
+                             + wzm * u[:-2, 1:-1, 1:-1] + wzp * u[2:, 1:-1, 1:-1])
+    return out
+
+
 def life(u: torch.Tensor, rule: str = "B3/S23") -> torch.Tensor:
     """Game of Life with a held (dead) frame, Conway's B3/S23 or any Life-like ``rule``; ``u`` is
     (h, 1, w) or (h, w) uint8. Integer arithmetic: the neighbour count, then a lookup in the rule's
@@ -105,6 +117,9 @@ def step(kind: str, u: torch.Tensor, **coef) -> torch.Tensor:
                      coef.get("c3", 3.0 / 160.0))
     if kind == "box9":
         return box9(u, coef.get("c0", 1.0 / 3.0), coef.get("c1", 2.0 / 15.0), coef.get("c2", 1.0 / 30.0))
+    if kind == "star7":
+        return star7(u, coef.get("c0", 0.30), coef.get("wxm", 0.20), coef.get("wxp", 0.20), coef.get("wym", 0.10),
+                     coef.get("wyp", 0.10), coef.get("wzm", 0.05), coef.get("wzp", 0.05))
     if kind == "life":
         return life(u, coef.get("rule", "B3/S23"))
     raise ValueError(kind)
