@@ -84,6 +84,8 @@ def main():
         prob = m.mdf2d(h=nz, w=nx, dtype=a.dtype)
     elif a.kind == "box9":
         prob = m.box9(h=nz, w=nx, dtype=a.dtype)
+    elif a.kind == "conv9":
+        prob = m.conv9(h=nz, w=nx, dtype=a.dtype)
     elif a.kind == "star7":
         prob = m.star7(nx=nx, ny=ny, nz=nz, dtype=a.dtype)
     else:

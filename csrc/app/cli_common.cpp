@@ -40,7 +40,7 @@ struct Opts {
   bool compat = false;
   bool ref_precision = false;
   std::string rule;  // --rule B36/S23 (Life); empty = Conway's B3/S23
-  std::string weights;  // --weights c0,xm,xp,ym,yp,zm,zp (star7); empty = the defaults
+  std::string weights;  // --weights: seven numbers (star7) or nine, row-major (conv9); empty = the defaults
   int temporal = 0;  // 0 = auto: hip_fused_depth on HIP where a fused kernel exists, else 1
   int py = 1;        // --py: ranks along y of a (z, y) pencil split
   bool profile = false;
@@ -52,9 +52,9 @@ void usage(const char* prog) {
   std::printf(
       "usage: %s [options]\n"
       "  With no size/step options the reference dialogue runs on stdin (generations, height, width).\n"
-      "  --stencil 5|7|9|27|star7|life  stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
+      "  --stencil 5|7|9|27|star7|conv9|life  stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
       "                            9 = 2D 9-pt with --c0 --c1 --c2, default 1/3, 2/15, 1/30; star7 = 3D\n"
-      "                            7-pt with seven weights, see --weights)\n"
+      "                            7-pt with seven weights, conv9 = 2D 9-pt with nine weights, see --weights)\n"
       "  --n N | --nx --ny --nz    3D grid (N^3) ; 2D: --h ROWS --w COLS\n"
       "  --steps K (--iters, -g)   time steps / generations ; --warmup W untimed steps first\n"
       "  --dtype f32|f64           element type (life is always u8)\n"
@@ -71,6 +71,8 @@ void usage(const char* prog) {
       "  --r R | --c0 --c1 --c2 --c3   update coefficients\n"
       "  --weights c0,xm,xp,ym,yp,zm,zp  star7: the centre weight and the weights of u(x-1), u(x+1), u(y-1),\n"
       "                            u(y+1), u(z-1), u(z+1); default 0.3,0.2,0.2,0.1,0.1,0.05,0.05\n"
+      "  --weights nw,n,ne,w,c,e,sw,s,se  conv9: the nine weights, row-major (the row above first); default\n"
+      "                            0.06,0.10,0.02,0.14,0.36,0.14,0.02,0.10,0.06\n"
       "  --ref-precision           2D MDF: the reference's fp32-sum / fp64-scale evaluation of the update\n"
       "                            (default in the reference dialogue; single-step sweeps)\n"
       "  --rule B<n..>/S<n..>      Life: any outer-totalistic Moore rule, e.g. B36/S23 (HighLife),\n"
@@ -266,8 +268,11 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     // the reference dialogue reproduces the reference's arithmetic too (MDF_kernel.cu:20, D17)
     spec.coef.ref_precision = kind == StencilKind::Jacobi5 && (o.ref_precision || o.compat);
     if (!o.weights.empty()) {
-      MDFX_CHECK(kind == StencilKind::Star7, "--weights goes with --stencil star7");
-      star7_weights_from_text(o.weights, spec.coef);
+      MDFX_CHECK(kind == StencilKind::Star7 || kind == StencilKind::Conv9, "--weights goes with --stencil star7 or conv9");
+      if (kind == StencilKind::Conv9)
+        conv9_weights_from_text(o.weights, spec.coef);
+      else
+        star7_weights_from_text(o.weights, spec.coef);
     }
     if (!o.rule.empty()) {
       MDFX_CHECK(kind == StencilKind::Life, "--rule goes with --stencil life");
@@ -353,7 +358,7 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     // ---- initial condition ----------------------------------------------------------------
     std::string ik = o.init;
     if (ik.empty())
-      ik = (kind == StencilKind::Jacobi5 || kind == StencilKind::Box9) ? "dirichlet"
+      ik = (kind == StencilKind::Jacobi5 || kind == StencilKind::Box9 || kind == StencilKind::Conv9) ? "dirichlet"
                                         : (kind == StencilKind::Life ? (o.compat ? "compat" : "life") : "random");
     if (!o.resume.empty()) {
       solver.load_checkpoint(o.resume);

@@ -81,6 +81,7 @@ const char* stencil_name(StencilKind k) {
     case StencilKind::Box27: return "box27";
     case StencilKind::Box9: return "box9";
     case StencilKind::Star7: return "star7";
+    case StencilKind::Conv9: return "conv9";
   }
   return "?";
 }
@@ -92,7 +93,8 @@ StencilKind stencil_from_name(const std::string& s) {
   if (s == "box27" || s == "27" || s == "27pt") return StencilKind::Box27;
   if (s == "box9" || s == "9" || s == "9pt") return StencilKind::Box9;
   if (s == "star7" || s == "s7") return StencilKind::Star7;
-  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|star7|life)");
+  if (s == "conv9" || s == "c9" || s == "3x3") return StencilKind::Conv9;
+  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|star7|conv9|life)");
 }
 
 void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive) {
@@ -128,8 +130,8 @@ void star7_check_weights(const StencilCoef& c) {
     if (!std::isfinite(v)) MDFX_FAIL("star7 weights must be finite (c0, xm, xp, ym, yp, zm, zp)");
 }
 
-void star7_weights_from_text(const std::string& s, StencilCoef& coef) {
-  double w[7];
+// exactly `count` comma-separated finite numbers into w; false for anything else
+static bool weights_from_text(const std::string& s, double* w, int count) {
   int n = 0;
   size_t pos = 0;
   bool ok = !s.empty();
@@ -138,11 +140,16 @@ void star7_weights_from_text(const std::string& s, StencilCoef& coef) {
     const std::string part = s.substr(pos, end - pos);
     char* tail = nullptr;
     const double v = std::strtod(part.c_str(), &tail);
-    ok = !part.empty() && tail && *tail == '\0' && std::isfinite(v) && n < 7;
+    ok = !part.empty() && tail && *tail == '\0' && std::isfinite(v) && n < count;
     if (ok) w[n++] = v;
     pos = end + 1;
   }
-  if (!ok || n != 7)
+  return ok && n == count;
+}
+
+void star7_weights_from_text(const std::string& s, StencilCoef& coef) {
+  double w[7];
+  if (!weights_from_text(s, w, 7))
     MDFX_FAIL("star7 weights '" + s + "': expected seven comma-separated finite numbers c0,xm,xp,ym,yp,zm,zp");
   coef.c0 = w[0];
   coef.wxm = w[1];
@@ -151,6 +158,18 @@ void star7_weights_from_text(const std::string& s, StencilCoef& coef) {
   coef.wyp = w[4];
   coef.wzm = w[5];
   coef.wzp = w[6];
+}
+
+void conv9_check_weights(const StencilCoef& c) {
+  for (double v : c.w9)
+    if (!std::isfinite(v)) MDFX_FAIL("conv9 weights must be finite (nine, row-major)");
+}
+
+void conv9_weights_from_text(const std::string& s, StencilCoef& coef) {
+  double w[9];
+  if (!weights_from_text(s, w, 9))
+    MDFX_FAIL("conv9 weights '" + s + "': expected nine comma-separated finite numbers, row-major (nw,n,ne,w,c,e,sw,s,se)");
+  std::copy(w, w + 9, coef.w9);
 }
 
 FieldLayout FieldLayout::make(Extent3 g, int64_t z0, int64_t z1, int halo, DType dt, int64_t y0, int64_t y1, int hy) {

@@ -159,6 +159,31 @@ void box9_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const St
   if (RES) *resid += acc;
 }
 
+// 2D 9-point with nine weights: sm::conv9, per-row partials exactly as the device kernels
+template <class T, bool RES>
+void conv9_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const StencilCoef& cf, double* resid) {
+  T w[9];
+  for (int i = 0; i < 9; ++i) w[i] = (T)cf.w9[i];
+  double acc = 0.0;
+#pragma omp parallel for schedule(static) reduction(+ : acc) if ((le - lb) * g.nx > 262144)
+  for (int64_t lz = lb; lz < le; ++lz) {
+    const int64_t gz = lz + g.gz_off;
+    const T* __restrict__ c = in + lz * g.plane;
+    T* __restrict__ o = out + lz * g.plane;
+    if (gz > 0 && gz < g.gnz - 1 && g.nx > 2) {
+      const T *__restrict__ zm = c - g.plane, *__restrict__ zp = c + g.plane;
+      o[0] = c[0];
+#pragma omp simd
+      for (int64_t x = 1; x < g.nx - 1; ++x) o[x] = sm::conv9<T>(zm + x, c + x, zp + x, w);
+      o[g.nx - 1] = c[g.nx - 1];
+    } else {
+      std::memcpy(o, c, (size_t)g.nx * sizeof(T));
+    }
+    if (RES) acc += row_resid(o, c, g.nx);
+  }
+  if (RES) *resid += acc;
+}
+
 // 3D 7-point star with seven weights: sm::star7, the chain the device kernels evaluate
 template <class T, bool RES>
 void star7_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const StencilCoef& cf, double* resid) {
@@ -259,6 +284,12 @@ void region_t(const StencilSpec& spec, const RegionArgs& a) {
         star7_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       else
         star7_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      break;
+    case StencilKind::Conv9:
+      if (spec.dtype == DType::F32)
+        conv9_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      else
+        conv9_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       break;
     case StencilKind::Life:
       if (spec.conway())

@@ -40,6 +40,7 @@ Solver::Solver(const StencilSpec& spec, Extent3 global, int nranks, std::vector<
   else
     MDFX_CHECK(global_.ny >= 1, "bad ny");
   if (spec_.kind == StencilKind::Star7) star7_check_weights(spec_.coef);
+  if (spec_.kind == StencilKind::Conv9) conv9_check_weights(spec_.coef);
   if (spec_.kind == StencilKind::Life) MDFX_CHECK(spec_.dtype == DType::U8, "life cells are u8");
   if (spec_.kind != StencilKind::Life)
     MDFX_CHECK(spec_.dtype == DType::F32 || spec_.dtype == DType::F64, "stencil dtype must be f32 or f64");

@@ -52,11 +52,12 @@ enum class StencilKind : int {
   Box27 = 3,    // 3D 27-point weighted stencil (BASELINE.json config 4)
   Box9 = 4,     // 2D 9-point weighted stencil (centre, edge and corner weights)
   Star7 = 5,    // 3D 7-point star with seven independent weights (anisotropy, advection, decay)
+  Conv9 = 6,    // 2D 9-point stencil with nine independent weights (any 3x3 linear update)
 };
 const char* stencil_name(StencilKind k);
 StencilKind stencil_from_name(const std::string& s);
 inline bool stencil_is_2d(StencilKind k) {
-  return k == StencilKind::Jacobi5 || k == StencilKind::Life || k == StencilKind::Box9;
+  return k == StencilKind::Jacobi5 || k == StencilKind::Life || k == StencilKind::Box9 || k == StencilKind::Conv9;
 }
 
 // Coefficients. Jacobi5/Heat7: u' = u + r * (sum_neighbours - 2d * u). Box27:
@@ -64,12 +65,15 @@ inline bool stencil_is_2d(StencilKind k) {
 // u' = c0*u + c1*sum(4 edges) + c2*sum(4 corners) (c3 unused). Star7:
 // u' = c0*u + wxm*u(x-1) + wxp*u(x+1) + wym*u(y-1) + wyp*u(y+1) + wzm*u(z-1) + wzp*u(z+1), evaluated as
 // sm::star7; its default c0 is kStar7C0 (c0 is shared with the box families, whose default is 0.25).
-// Sum |w| <= 1 keeps the max-norm from growing.
+// Sum |w| <= 1 keeps the max-norm from growing. Conv9: u' = sum over dz, dx in {-1, 0, 1} of
+// w9[3*(dz+1) + (dx+1)] * u(z+dz, x+dx) (row-major; z is the row axis, x runs along the row), evaluated as
+// sm::conv9. Its default is a diffusion with a positive cross term, weights non-negative and summing to 1.
 constexpr double kStar7C0 = 0.30;
 struct StencilCoef {
   double r = -1.0;  // < 0 -> default 1/(2d) (Jacobi)
   double c0 = 0.25, c1 = 1.0 / 20.0, c2 = 1.0 / 40.0, c3 = 3.0 / 160.0;
   double wxm = 0.20, wxp = 0.20, wym = 0.10, wyp = 0.10, wzm = 0.05, wzp = 0.05;  // Star7 neighbour weights
+  double w9[9] = {0.06, 0.10, 0.02, 0.14, 0.36, 0.14, 0.02, 0.10, 0.06};  // Conv9 weights, row-major
   // 2D MDF only: evaluate the update exactly as the reference does (sm::jacobi5_ref: fp32 sum and
   // -4u, fp64 scale and add, one more rounding at the store) instead of wholly in the field type.
   // See StencilSpec::mixed_update() for when the two can differ at all.
@@ -89,6 +93,11 @@ std::string life_rule_name(uint32_t birth, uint32_t survive);  // canonical form
 // a non-number or a non-finite value throws an Error that names the text.
 void star7_weights_from_text(const std::string& s, StencilCoef& coef);
 void star7_check_weights(const StencilCoef& coef);  // every Star7 weight finite, else an Error
+
+// Conv9 weights as text: nine comma-separated finite numbers, row-major (the row above first, west to
+// east). Any other count, a non-number or a non-finite value throws an Error that names the text.
+void conv9_weights_from_text(const std::string& s, StencilCoef& coef);
+void conv9_check_weights(const StencilCoef& coef);  // every Conv9 weight finite, else an Error
 
 struct StencilSpec {
   StencilKind kind = StencilKind::Heat7;

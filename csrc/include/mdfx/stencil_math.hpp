@@ -115,6 +115,34 @@ MDFX_HDI T star7(T c, T xm, T xp, T ym, T yp, T zm, T zp, const Star7W<T>& w) {
   return star7_finish<T>(star7_P<T>(B, zm, w.zm), zp, w.zp);
 }
 
+// 2D 9-point with nine independent weights (conv9; rows are the z axis), ordered for a march over rows.
+// w is row-major: w[3*(dz+1) + (dx+1)] multiplies u(z+dz, x+dx). An arriving row p with c = v(x),
+// l = v(x-1), r = v(x+1) yields three horizontal sums, each one multiply and two fmas:
+//   T(p) = fma(w2, r, fma(w0, l, w1 * c))   what row p gives output row p + 1 (it is that row's dz = -1)
+//   M(p) = fma(w5, r, fma(w3, l, w4 * c))   what row p gives itself
+//   B(p) = fma(w8, r, fma(w6, l, w7 * c))   what row p gives output row p - 1 (that row's dz = +1)
+//   u'(z) = (T(z-1) + M(z)) + B(z+1)
+template <class T>
+struct Conv9W {
+  T w[9];  // row-major, in the field type
+};
+template <class T>
+MDFX_HDI T conv9_row(T c, T l, T r, T wl, T wc, T wr) {
+  return fmaT(wr, r, fmaT(wl, l, wc * c));
+}
+template <class T>
+MDFX_HDI T conv9_combine(T t_m, T m_c, T b_p) {
+  return (t_m + m_c) + b_p;
+}
+// one cell from its 3x3 neighbourhood: zm / zc / zp point at v(x) of rows z-1 / z / z+1
+template <class T>
+MDFX_HDI T conv9(const T* zm, const T* zc, const T* zp, const T* w) {
+  const T t = conv9_row<T>(zm[0], zm[-1], zm[1], w[0], w[1], w[2]);
+  const T m = conv9_row<T>(zc[0], zc[-1], zc[1], w[3], w[4], w[5]);
+  const T b = conv9_row<T>(zp[0], zp[-1], zp[1], w[6], w[7], w[8]);
+  return conv9_combine<T>(t, m, b);
+}
+
 // Life: T = sum of the 3x3 block including self.
 MDFX_HDI unsigned char life_rule(unsigned t, unsigned char alive) {
   return (unsigned char)((t == 3u) | ((t == 4u) & (alive != 0)));

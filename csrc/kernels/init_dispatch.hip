@@ -39,6 +39,9 @@ void launch_box27(const Geo& g, const T* in, T* out, const StencilCoef& c, doubl
 // 2D 9-point: box9_wave (steps = 1) and box9_tbk (2, 3, 4, 6, 8 fused steps), stencil_box9.hip
 template <class T>
 void launch_box9(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
+// 2D 9-point with nine weights: conv9_tbk (1, 2, 3, 4, 6, 8 steps per sweep), stencil_conv9.hip
+template <class T>
+void launch_conv9(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
 // 3D 7-point star with seven weights: star7_tbk (1, 2, 3, 4 steps per sweep), stencil_star7.hip
 template <class T>
 void launch_star7(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
@@ -264,6 +267,7 @@ bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int ste
   if (spec.kind == StencilKind::Jacobi5)  // deep temporal blocking of the 2D problems
     return (spec.dtype == DType::F32 || spec.dtype == DType::F64) && k2d;  // ref precision too (jacobi5_tbk REF)
   if (spec.kind == StencilKind::Box9) return k2d;  // box9_tbk
+  if (spec.kind == StencilKind::Conv9) return k2d;  // conv9_tbk
   if (spec.kind == StencilKind::Star7) return steps <= 4;  // star7_tbk: any nx, ny, nz
   // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
   if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;
@@ -299,6 +303,13 @@ int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
       // 1123 / 1706 / 2277 / 3400 / 4611), fp64 281 / 564 / 835 / 1104 / 1759 / 1901 (304 / 613 / 904 /
       // 1203 / 1639 / 2276); the sweeps stay at the memory roof up to K = 6 (profiles/r07_box9/)
       return 8;
+    case StencilKind::Conv9:
+      // 16384^2 fp32 542 / 1094 / 1552 / 2096 / 2554 / 2407 GCells/s for K = 1 / 2 / 3 / 4 / 6 / 8 (box9 in
+      // the same call: 558 / 1166 / 1647 / 2177 / 3454 / 3607), fp64 276 / 551 / 905 / 1090 / 1556 / 1735
+      // (280 / 565 / 836 / 1104 / 1761 / 1901): at the memory roof up to K = 4, bound by its arithmetic
+      // (11 VALU ops per cell and level against box9's 7) from K = 6 on; fp32 K = 8 costs 1.8 single
+      // steps per sweep and loses to K = 6 (profiles/r10_conv9/)
+      return spec.dtype == DType::F64 ? 8 : 6;
     case StencilKind::Star7:
       // K = 3 is the fastest per step for both dtypes: 512^3 fp32 565 / 879 / 995 / 666 GCells/s for
       // K = 1 / 2 / 3 / 4 (heat7's kernels in the same call: 669 / 1300 / 1650 / 2031), fp64 294 / 473 /
@@ -373,6 +384,14 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
     // against 1.99 for 6 + 3.)
     static const double f32[9] = {0.0, 1.0, 0.96, 1.02, 1.02, 0.0, 0.97, 0.0, 1.24};
     static const double f64[9] = {0.0, 1.0, 1.00, 1.01, 1.02, 0.0, 0.96, 0.0, 1.18};
+    const double c = (spec.dtype == DType::F64 ? f64 : f32)[steps];
+    if (c > 0.0) return c;
+  }
+  if (spec.kind == StencilKind::Conv9 && steps <= 8 && nx >= 8192) {
+    // conv9_tbk's per-sweep times against its single step at 16384^2 (profiles/r10_conv9/): one pass over
+    // memory up to K = 4, arithmetic-bound beyond (fp32 K = 8: more than K = 6 + 2)
+    static const double f32[9] = {0.0, 1.0, 0.99, 1.05, 1.04, 0.0, 1.27, 0.0, 1.81};
+    static const double f64[9] = {0.0, 1.0, 1.00, 0.92, 1.01, 0.0, 1.07, 0.0, 1.27};
     const double c = (spec.dtype == DType::F64 ? f64 : f32)[steps];
     if (c > 0.0) return c;
   }
@@ -472,6 +491,11 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
         dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
       else
         dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
+    } else if (spec.kind == StencilKind::Conv9) {
+      if (spec.dtype == DType::F32)
+        dev::launch_conv9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
+      else
+        dev::launch_conv9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
     } else if (spec.kind == StencilKind::Star7) {
       if (spec.dtype == DType::F32)
         dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
@@ -556,6 +580,12 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
           dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
         else
           dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
+        break;
+      case StencilKind::Conv9:
+        if (spec.dtype == DType::F32)
+          dev::launch_conv9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
+        else
+          dev::launch_conv9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
         break;
       case StencilKind::Star7:
         if (spec.dtype == DType::F32)

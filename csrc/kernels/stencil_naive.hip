@@ -107,6 +107,29 @@ __global__ __launch_bounds__(256) void naive_box27(const T* __restrict__ in, T* 
   if (RES) wave_atomic_add(resid, acc);
 }
 
+template <class T, bool RES>
+__global__ __launch_bounds__(256) void naive_conv9(const T* __restrict__ in, T* __restrict__ out, Geo g,
+                                                   sm::Conv9W<T> k, double* __restrict__ resid) {
+  const int64_t n = g.nx * (g.lz_end - g.lz_begin);
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t x = i % g.nx, lz = g.lz_begin + i / g.nx;
+    const int64_t gz = lz + g.gz_off;
+    const int64_t idx = lz * g.plane + x;
+    const T c = in[idx];
+    T o = c;
+    if (x > 0 && x < g.nx - 1 && gz > 0 && gz < g.gnz - 1)
+      o = sm::conv9<T>(in + idx - g.plane, in + idx, in + idx + g.plane, k.w);
+    out[idx] = o;
+    if (RES) {
+      const double d = (double)o - (double)c;
+      acc += d * d;
+    }
+  }
+  if (RES) wave_atomic_add(resid, acc);
+}
+
 // the rule of a Life kernel: Conway's fixed compare (sm::life_rule) or the two masks of any other
 // outer-totalistic rule (sm::life_like); passed last, so Conway's kernel arguments stay where they were
 struct ConwayRule {
@@ -201,6 +224,17 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
         launch_star7_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
       else
         launch_star7_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
+      break;
+    case StencilKind::Conv9:
+      if (spec.dtype == DType::F32) {
+        sm::Conv9W<float> k;
+        for (int i = 0; i < 9; ++i) k.w[i] = (float)spec.coef.w9[i];
+        MDFX_NAIVE(naive_conv9, float, k);
+      } else {
+        sm::Conv9W<double> k;
+        for (int i = 0; i < 9; ++i) k.w[i] = spec.coef.w9[i];
+        MDFX_NAIVE(naive_conv9, double, k);
+      }
       break;
     case StencilKind::Life: {
       const TableRule tr{spec.coef.birth, spec.coef.survive};

@@ -8,7 +8,10 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cstring>
+#include <iterator>
+#include <vector>
 
 #include "mdfx/devsync.hpp"
 #include "mdfx/solver.hpp"
@@ -78,10 +81,17 @@ py::capsule make_dlpack(void* data, int device, DType dt, std::vector<int64_t> s
   });
 }
 
+// Conv9's default weights (StencilCoef::w9), row-major
+const std::vector<double> kConv9Default = [] {
+  const StencilCoef c;
+  return std::vector<double>(c.w9, c.w9 + 9);
+}();
+
 StencilSpec make_spec(const std::string& kind, const std::string& dtype, double r, double c0,
                       double c1, double c2, double c3, bool ref_precision = false,
                       const std::string& rule = "B3/S23", double wxm = 0.20, double wxp = 0.20, double wym = 0.10,
-                      double wyp = 0.10, double wzm = 0.05, double wzp = 0.05) {
+                      double wyp = 0.10, double wzm = 0.05, double wzp = 0.05,
+                      const std::vector<double>& w9 = kConv9Default) {
   StencilSpec s;
   s.coef.ref_precision = ref_precision;
   life_rule_from_name(rule, s.coef.birth, s.coef.survive);
@@ -99,6 +109,9 @@ StencilSpec make_spec(const std::string& kind, const std::string& dtype, double 
   s.coef.wzm = wzm;
   s.coef.wzp = wzp;
   if (s.kind == StencilKind::Star7) star7_check_weights(s.coef);
+  if (w9.size() != 9) throw Error(format("w9 takes nine weights, row-major (got %d)", (int)w9.size()));
+  std::copy(w9.begin(), w9.end(), s.coef.w9);
+  if (s.kind == StencilKind::Conv9) conv9_check_weights(s.coef);
   return s;
 }
 
@@ -217,8 +230,9 @@ class PySolver {
            const std::string& transport, py::bytes unique_id, py::object callbacks, bool overlap,
            bool sync_debug, int residual_every, bool graph, double timeout_s, double r, double c0,
            double c1, double c2, double c3, int temporal, bool ref_precision, int pencil_py, bool share_gpu,
-           const std::string& rule, double wxm, double wxp, double wym, double wyp, double wzm, double wzp) {
-    const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule, wxm, wxp, wym, wyp, wzm, wzp);
+           const std::string& rule, double wxm, double wxp, double wym, double wyp, double wzm, double wzp,
+           const std::vector<double>& w9) {
+    const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule, wxm, wxp, wym, wyp, wzm, wzp, w9);
     if (devices.size() == 1 && local_ranks.size() > 1) devices.assign(local_ranks.size(), devices[0]);
     if (devices.size() != local_ranks.size())
       throw Error("devices must have one entry per local rank (or a single entry)");
@@ -342,7 +356,7 @@ PYBIND11_MODULE(_mdfx, m) {
          int64_t ny, int64_t nz, int64_t z0, int64_t z1, int halo, int64_t lz_begin, int64_t lz_end,
          int device, uintptr_t stream, uintptr_t resid, double r, double c0, double c1, double c2,
          double c3, int steps, bool ref_precision, int64_t lz2_begin, int64_t lz2_end, const std::string& rule,
-         double wxm, double wxp, double wym, double wyp, double wzm, double wzp) {
+         double wxm, double wxp, double wym, double wyp, double wzm, double wzp, const std::vector<double>& w9) {
         RegionArgs a;
         a.lz2_begin = lz2_begin;
         a.lz2_end = lz2_end;
@@ -353,7 +367,7 @@ PYBIND11_MODULE(_mdfx, m) {
         a.lz_end = lz_end;
         a.resid = (double*)resid;
         a.steps = steps;
-        const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule, wxm, wxp, wym, wyp, wzm, wzp);
+        const StencilSpec spec = make_spec(kind, dtype, r, c0, c1, c2, c3, ref_precision, rule, wxm, wxp, wym, wyp, wzm, wzp, w9);
         if (device < 0)
           cpu_stencil(spec, a);
         else
@@ -365,7 +379,8 @@ PYBIND11_MODULE(_mdfx, m) {
       py::arg("resid_ptr") = 0, py::arg("r") = -1.0, py::arg("c0") = 0.25, py::arg("c1") = 0.05,
       py::arg("c2") = 0.025, py::arg("c3") = 3.0 / 160.0, py::arg("steps") = 1, py::arg("ref_precision") = false,
       py::arg("lz2_begin") = 0, py::arg("lz2_end") = 0, py::arg("rule") = "B3/S23", py::arg("wxm") = 0.20, py::arg("wxp") = 0.20,
-      py::arg("wym") = 0.10, py::arg("wyp") = 0.10, py::arg("wzm") = 0.05, py::arg("wzp") = 0.05);
+      py::arg("wym") = 0.10, py::arg("wyp") = 0.10, py::arg("wzm") = 0.05, py::arg("wzp") = 0.05,
+      py::arg("w9") = kConv9Default);
   m.def(
       "init_field",
       [](const std::string& kind, const std::string& dtype, uintptr_t buf, int64_t nx, int64_t ny,
@@ -443,7 +458,8 @@ PYBIND11_MODULE(_mdfx, m) {
       .def(py::init<const std::string&, const std::string&, int64_t, int64_t, int64_t, int,
                     std::vector<int>, std::vector<int>, const std::string&, py::bytes, py::object,
                     bool, bool, int, bool, double, double, double, double, double, double, int, bool, int, bool,
-                    const std::string&, double, double, double, double, double, double>(),
+                    const std::string&, double, double, double, double, double, double,
+                    const std::vector<double>&>(),
            py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
            py::arg("nranks"), py::arg("local_ranks"), py::arg("devices"), py::arg("transport"),
            py::arg("unique_id") = py::bytes(""), py::arg("callbacks") = py::none(),
@@ -452,7 +468,8 @@ PYBIND11_MODULE(_mdfx, m) {
            py::arg("c0") = 0.25, py::arg("c1") = 0.05, py::arg("c2") = 0.025,
            py::arg("c3") = 3.0 / 160.0, py::arg("temporal") = 1, py::arg("ref_precision") = false, py::arg("py") = 1,
            py::arg("share_gpu") = false, py::arg("rule") = "B3/S23", py::arg("wxm") = 0.20, py::arg("wxp") = 0.20,
-           py::arg("wym") = 0.10, py::arg("wyp") = 0.10, py::arg("wzm") = 0.05, py::arg("wzp") = 0.05)
+           py::arg("wym") = 0.10, py::arg("wyp") = 0.10, py::arg("wzm") = 0.05, py::arg("wzp") = 0.05,
+           py::arg("w9") = kConv9Default)
       .def("close", &PySolver::close)
       .def("phase_times",
            [](PySolver& p) {

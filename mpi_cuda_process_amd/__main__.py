@@ -21,7 +21,7 @@ from .utils import metrics_record, print_array
 
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m mpi_cuda_process_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("--stencil", default="7", help="5 | 7 | 9 | 27 | star7 | life (aliases: mdf, heat7, box9, box27, s7, gol)")
+    p.add_argument("--stencil", default="7", help="5 | 7 | 9 | 27 | star7 | conv9 | life (aliases: mdf, heat7, box9, box27, s7, c9, 3x3, gol)")
     p.add_argument("--n", type=int, default=0)
     p.add_argument("--nx", type=int, default=0)
     p.add_argument("--ny", type=int, default=0)
@@ -49,8 +49,9 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--rule", default="B3/S23",
                    help="life: any Life-like rule in B/S notation, e.g. B36/S23, B3678/S34678, B2/S")
-    p.add_argument("--weights", default="", metavar="c0,xm,xp,ym,yp,zm,zp",
-                   help="star7: the seven weights, comma-separated (default 0.3,0.2,0.2,0.1,0.1,0.05,0.05)")
+    p.add_argument("--weights", default="", metavar="W,W,...",
+                   help="star7: the seven weights c0,xm,xp,ym,yp,zm,zp (default 0.3,0.2,0.2,0.1,0.1,0.05,0.05); "
+                        "conv9: the nine weights, row-major (default 0.06,0.10,0.02,0.14,0.36,0.14,0.02,0.10,0.06)")
     p.add_argument("--resume", default="")
     p.add_argument("--dump", default="", help="write the final grid (checkpoint format) to this directory")
     p.add_argument("--print", action="store_true", help="print_array dump of the final grid (rank 0)")
@@ -62,10 +63,14 @@ def _problem(a):
     from .models import from_name
 
     kind = from_name(a.stencil).kind  # resolve aliases
-    if kind in ("jacobi5", "life", "box9"):
+    if a.weights and kind not in ("star7", "conv9"):
+        raise SystemExit("--weights goes with --stencil star7 or conv9")
+    if kind in ("jacobi5", "life", "box9", "conv9"):
         h = a.h or a.nz or a.n or 256
         w = a.w or a.nx or a.n or 256
         kw = dict(h=h, w=w)
+        if a.weights:
+            kw["w9"] = _weights(a.weights, 9)
         if kind != "life":
             kw["dtype"] = a.dtype
         else:
@@ -75,23 +80,25 @@ def _problem(a):
     n = a.n or 256
     kw = {}
     if a.weights:
-        if kind != "star7":
-            raise SystemExit("--weights goes with --stencil star7")
-        kw = _weights(a.weights)
+        kw = dict(zip(("c0", "wxm", "wxp", "wym", "wyp", "wzm", "wzp"), _weights(a.weights, 7)))
     return from_name(kind, nx=a.nx or n, ny=a.ny or n, nz=a.nz or n, dtype=a.dtype, **kw).with_init(seed=a.seed)
 
 
-def _weights(text):
-    """--weights c0,xm,xp,ym,yp,zm,zp -> star7 keyword arguments; anything else is an error naming the text."""
+def _weights(text, count):
+    """--weights -> seven numbers c0,xm,xp,ym,yp,zm,zp (star7) or nine, row-major (conv9); anything else is
+    an error naming the text and the expected count."""
     import math
 
     try:
         w = [float(t) for t in text.split(",")]
     except ValueError:
         w = []
-    if len(w) != 7 or not all(math.isfinite(v) for v in w):
+    if len(w) != count or not all(math.isfinite(v) for v in w):
+        if count == 9:
+            raise SystemExit("conv9 weights %r: expected nine comma-separated finite numbers, row-major "
+                             "(nw,n,ne,w,c,e,sw,s,se)" % text)
         raise SystemExit("star7 weights %r: expected seven comma-separated finite numbers c0,xm,xp,ym,yp,zm,zp" % text)
-    return dict(zip(("c0", "wxm", "wxp", "wym", "wyp", "wzm", "wzp"), w))
+    return w
 
 
 def main(argv=None) -> int:

@@ -13,6 +13,8 @@ the default initial condition. Families (reference parity in brackets):
 * :func:`box9`    — 2D 9-point weighted stencil (centre, edge and corner weights), Dirichlet edges
 * :func:`star7`   — 3D 7-point star with seven independent weights (anisotropic grids and conductivities,
   constant-velocity advection-diffusion, decay), Dirichlet faces
+* :func:`conv9`   — 2D 9-point stencil with nine independent weights (any 3x3 linear update: upwind
+  advection-diffusion, anisotropic conductivities, a full diffusion tensor, blur, sharpening), Dirichlet edges
 
 2D grids are stored as ``nx = w, ny = 1, nz = h``: rows are the slab axis, exactly like the
 reference's row split (MDF_kernel.cu:30,54).
@@ -23,8 +25,11 @@ from __future__ import annotations
 from dataclasses import dataclass, field, replace
 from typing import Optional
 
-KINDS = ("jacobi5", "life", "heat7", "box27", "box9", "star7")
-KINDS_2D = ("jacobi5", "life", "box9")
+KINDS = ("jacobi5", "life", "heat7", "box27", "box9", "star7", "conv9")
+KINDS_2D = ("jacobi5", "life", "box9", "conv9")
+
+# the default weights of conv9, row-major: a diffusion with a positive cross term; non-negative, summing to 1
+CONV9_DEFAULT = (0.06, 0.10, 0.02, 0.14, 0.36, 0.14, 0.02, 0.10, 0.06)
 
 
 @dataclass(frozen=True)
@@ -58,6 +63,8 @@ class Problem:
     wyp: float = 0.10
     wzm: float = 0.05
     wzp: float = 0.05
+    # conv9 only: nine weights, row-major; w9[3*(dz+1) + (dx+1)] multiplies u(z+dz, x+dx) (z the row, x along it)
+    w9: tuple = CONV9_DEFAULT
     # 2D MDF: evaluate the update exactly as the reference does (fp32 sum, fp64 scale and add;
     # MDF_kernel.cu:20) instead of wholly in the field type; single-step sweeps only
     ref_precision: bool = False
@@ -84,6 +91,9 @@ class Problem:
                 native().life_rule_parse(self.rule)
             except RuntimeError as e:
                 raise ValueError(str(e)) from None
+        object.__setattr__(self, "w9", tuple(float(v) for v in self.w9))
+        if len(self.w9) != 9:
+            raise ValueError("w9 takes nine weights, row-major (got %d)" % len(self.w9))
         for n in (self.nx, self.ny, self.nz):
             if n < 1:
                 raise ValueError("grid extents must be positive")
@@ -100,7 +110,7 @@ class Problem:
     def rate(self) -> float:
         if self.r >= 0:
             return self.r
-        return 0.25 if self.kind in ("jacobi5", "box9") else 1.0 / 6.0
+        return 0.25 if self.kind in ("jacobi5", "box9", "conv9") else 1.0 / 6.0
 
     @property
     def bytes_per_cell_per_step(self) -> int:
@@ -113,7 +123,7 @@ class Problem:
     def coef_kwargs(self) -> dict:
         return dict(r=self.r, c0=self.c0, c1=self.c1, c2=self.c2, c3=self.c3, ref_precision=self.ref_precision,
                     rule=self.rule, wxm=self.wxm, wxp=self.wxp, wym=self.wym, wyp=self.wyp, wzm=self.wzm,
-                    wzp=self.wzp)
+                    wzp=self.wzp, w9=self.w9)
 
     @property
     def conway(self) -> bool:
@@ -182,15 +192,26 @@ def star7(n: int = 256, nx: Optional[int] = None, ny: Optional[int] = None, nz: 
                    wyp=wyp, wzm=wzm, wzp=wzp, init=init or InitCondition(kind="random", seed=1))
 
 
+def conv9(h: int = 256, w: int = 256, dtype: str = "f32", w9=CONV9_DEFAULT,
+          init: Optional[InitCondition] = None) -> Problem:
+    """2D 9-point stencil with nine independent weights on an h x w grid, Dirichlet edges 100:
+    u'(z, x) = sum over dz, dx in {-1, 0, 1} of w9[3*(dz+1) + (dx+1)] * u(z+dz, x+dx), ``w9`` row-major
+    (z is the row, x runs along it). The default is a diffusion with a positive cross term whose weights
+    sum to 1. Weights must be finite; sum |w| <= 1 keeps the max-norm from growing."""
+    return Problem("conv9", nx=w, ny=1, nz=h, dtype=dtype, w9=tuple(w9),
+                   init=init or InitCondition(kind="dirichlet", edge=100.0, interior=0.0))
+
+
 def from_name(kind: str, **kw) -> Problem:
     aliases = {"5": "jacobi5", "mdf": "jacobi5", "jacobi5": "jacobi5", "life": "life", "gol": "life",
                "7": "heat7", "heat7": "heat7", "jacobi7": "heat7", "27": "box27", "box27": "box27",
-               "9": "box9", "9pt": "box9", "box9": "box9", "star7": "star7", "s7": "star7"}
+               "9": "box9", "9pt": "box9", "box9": "box9", "star7": "star7", "s7": "star7",
+               "conv9": "conv9", "c9": "conv9", "3x3": "conv9"}
     k = aliases.get(str(kind))
     if k is None:
         raise ValueError("unknown stencil %r" % kind)
     return {"jacobi5": mdf2d, "life": life2d, "heat7": heat3d, "box27": box27, "box9": box9,
-            "star7": star7}[k](**kw)
+            "star7": star7, "conv9": conv9}[k](**kw)
 
 
-__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "from_name", "KINDS"]
+__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "conv9", "from_name", "KINDS"]

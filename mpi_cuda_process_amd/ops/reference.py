@@ -80,6 +80,22 @@ def star7(u: torch.Tensor, c0: float = 0.30, wxm: float = 0.20, wxp: float = 0.2
     return out
 
 
+def conv9(u: torch.Tensor, w9=(0.06, 0.10, 0.02, 0.14, 0.36, 0.14, 0.02, 0.10, 0.06)) -> torch.Tensor:
+    """2D 9-point stencil with nine weights, row-major: ``w9[3*(dz+1) + (dx+1)]`` multiplies u(z+dz, x+dx);
+    ``u`` is (h, 1, w) or (h, w), edges held."""
+    squeeze = u.dim() == 2
+    v = u if squeeze else u[:, 0, :]
+    out = v.clone()
+    h, w = v.shape
+    if h >= 3 and w >= 3:
+        acc = torch.zeros_like(v[1:-1, 1:-1])
+        for dz in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                acc = acc + w9[3 * (dz + 1) + (dx + 1)] * v[1 + dz:h - 1 + dz, 1 + dx:w - 1 + dx]
+        out[1:-1, 1:-1] = acc
+    return out if squeeze else out.unsqueeze(1)
+
+
 def life(u: torch.Tensor, rule: str = "B3/S23") -> torch.Tensor:
     """Game of Life with a held (dead) frame, Conway's B3/S23 or any Life-like ``rule``; ``u`` is
     (h, 1, w) or (h, w) uint8. Integer arithmetic: the neighbour count, then a lookup in the rule's
@@ -120,6 +136,8 @@ def step(kind: str, u: torch.Tensor, **coef) -> torch.Tensor:
     if kind == "star7":
         return star7(u, coef.get("c0", 0.30), coef.get("wxm", 0.20), coef.get("wxp", 0.20), coef.get("wym", 0.10),
                      coef.get("wyp", 0.10), coef.get("wzm", 0.05), coef.get("wzp", 0.05))
+    if kind == "conv9":
+        return conv9(u, **({"w9": coef["w9"]} if "w9" in coef else {}))
     if kind == "life":
         return life(u, coef.get("rule", "B3/S23"))
     raise ValueError(kind)
