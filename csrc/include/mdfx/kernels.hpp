@@ -18,6 +18,17 @@ namespace mdfx {
 
 // One region update: out[planes lz_begin..lz_end) = stencil(in). Cells on the global boundary
 // (x, y or z equal to 0 or n-1) are Dirichlet: copied through unchanged.
+//
+// Footprint of a launch of K = steps fused steps (tests/test_gpu_footprint.py, docs/DESIGN.md section 2):
+//   writes: the region's planes (both regions'), columns [0, nx); the pad columns [nx, pitch) of
+//           those planes only as a copy of the input's pad; nothing else (no other owned plane,
+//           no ghost plane, no slack), and never `in`.
+//   reads:  planes [lz_begin-K, lz_end+K) for values that matter; anything else in the storage
+//           (pad, ghost planes outside the global grid, planes beyond that window, the slack)
+//           only into lanes that meet held or unowned cells.
+//   caller: pad, out-of-grid ghost planes and slack are finite and of moderate magnitude (held
+//           cells take a zero weight, which does not cancel Inf or NaN). The engine zero-fills
+//           them and only ever writes zero there.
 struct RegionArgs {
   const void* in = nullptr;
   void* out = nullptr;

@@ -1,5 +1,6 @@
 // Native unit tests (no framework dependency): slab math, layout, CPU oracle invariants,
 // decomposition invariance through the engine on the CPU backend, GPU engine when a device exists.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -186,26 +187,36 @@ static void test_graph() {
   }
 }
 
-// fused two- and three-step sweeps (halo 2 / 3; heat7_wtk for the 3D 7-point at K = 3) == single
-// steps, every stencil, several slab counts, ragged and x-tiled (wider than one block) rows
+// fused K-step sweeps (halo K) == single steps: every stencil at every fused depth its tuned kernels
+// have (heat7_tbk / heat7_wtk / heat7_wxk up to K = 5, box27_wxk at K = 3, box9_tbk / conv9_tbk up to 8,
+// star7_tbk up to 4, life_bits and, under a non-Conway rule, life_rule_bits up to 16), several slab
+// counts, ragged and x-tiled (wider than one block) rows. Each run takes two full-depth sweeps and a
+// tail, with a residual on the first; the devcheck build counts every one of these kernels'
+// out-of-allocation accesses.
 static void test_temporal(bool gpu) {
   struct C {
     StencilKind k;
     DType d;
     Extent3 g;
-  } cs[] = {{StencilKind::Heat7, DType::F32, {1100, 9, 23}},
-            {StencilKind::Heat7, DType::F64, {77, 13, 19}},
-            {StencilKind::Box27, DType::F32, {300, 11, 17}},
-            {StencilKind::Jacobi5, DType::F64, {700, 1, 29}},
-            {StencilKind::Life, DType::U8, {2100, 1, 31}}};
+    std::vector<int> depths;
+    const char* rule;
+  } cs[] = {{StencilKind::Heat7, DType::F32, {1100, 9, 23}, {1, 2, 3, 4, 5}, nullptr},
+            {StencilKind::Heat7, DType::F64, {77, 13, 19}, {1, 2, 3, 4, 5}, nullptr},
+            {StencilKind::Box27, DType::F32, {300, 11, 17}, {1, 2, 3}, nullptr},
+            {StencilKind::Jacobi5, DType::F64, {700, 1, 29}, {1, 2, 3}, nullptr},
+            {StencilKind::Life, DType::U8, {2100, 1, 31}, {1, 2, 3}, nullptr},
+            {StencilKind::Box9, DType::F32, {700, 1, 29}, {1, 2, 3, 4, 6, 8}, nullptr},
+            {StencilKind::Conv9, DType::F64, {300, 1, 31}, {1, 2, 3, 4, 6, 8}, nullptr},
+            {StencilKind::Star7, DType::F32, {130, 9, 17}, {1, 2, 3, 4}, nullptr},
+            {StencilKind::Life, DType::U8, {2100, 1, 53}, {1, 2, 3, 4, 6, 8, 12, 16}, "B36/S23"}};
   for (auto& c : cs)
     for (int p : {1, 3}) {
       std::vector<std::vector<char>> outs;
-      for (int t : {1, 2, 3}) {
-        if (t == 3 && c.k == StencilKind::Box27) continue;  // the 27-point fuses 2 steps at most
+      for (int t : c.depths) {
         StencilSpec s;
         s.kind = c.k;
         s.dtype = c.d;
+        if (c.rule) life_rule_from_name(c.rule, s.coef.birth, s.coef.survive);
         std::vector<int> ranks;
         std::vector<std::unique_ptr<Backend>> bes;
         for (int r = 0; r < p; ++r) {
@@ -214,12 +225,12 @@ static void test_temporal(bool gpu) {
         }
         SolverOptions o;
         o.temporal = t;
-        o.residual_every = 4;
+        o.residual_every = std::max(4, t);
         Solver sol(s, c.g, p, ranks, std::move(bes), gpu ? make_loopback_transport() : make_host_transport(), o);
         InitSpec is;
         is.kind = c.k == StencilKind::Life ? InitKind::LifeRandom : InitKind::Random;
         sol.init(is);
-        sol.run(9);
+        sol.run(std::max(9, 2 * c.depths.back() + 1));
         std::vector<char> out;
         for (int i = 0; i < p; ++i) {
           const FieldLayout& l = sol.layout(i);

@@ -91,6 +91,14 @@ def apply_stencil(problem: Problem, layout: FieldLayout, src: torch.Tensor, dst:
     (temporal blocking; needs ``layout.halo >= steps`` and valid ghosts that deep); the residual
     then covers the last step. ``second`` = (lz_begin, lz_end) of a second region updated by the
     same call (the engine's pair of boundary regions; one launch for the fused 3D 7-point sweep).
+
+    Footprint (``RegionArgs`` in kernels.hpp; tests/test_gpu_footprint.py): the call writes the
+    regions' planes, columns ``[0, nx)``, and the pad columns of those planes only as a copy of
+    ``src``'s pad; it writes nothing else in ``dst`` and never ``src``. It reads planes
+    ``[lz_begin - steps, lz_end + steps)`` for values that matter and anything else in the storage
+    only into lanes that meet held or unowned cells. The caller provides pad columns, ghost planes
+    outside the global grid and slack that are finite and of moderate magnitude
+    (:func:`alloc_field` zero-fills them; :func:`init_field` and the engine only ever write zero there).
     """
     _check(src, layout)
     _check(dst, layout)
