@@ -71,6 +71,8 @@ $(OBJ)/kernels/stencil_life_rule.o $(ASAN_DIR)/kernels/stencil_life_rule.o $(DCK
 $(OBJ)/kernels/stencil_star7.o $(ASAN_DIR)/kernels/stencil_star7.o $(DCK_DIR)/kernels/stencil_star7.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # conv9's nine scalar-register weights feed plain (unpacked) VALU multiplies and fmas
 $(OBJ)/kernels/stencil_conv9.o $(ASAN_DIR)/kernels/stencil_conv9.o $(DCK_DIR)/kernels/stencil_conv9.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# star13 is one multiply and twelve fmas per cell with three scalar-register weights, plain VALU ops too
+$(OBJ)/kernels/stencil_star13.o $(ASAN_DIR)/kernels/stencil_star13.o $(DCK_DIR)/kernels/stencil_star13.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 # the AVX2 + FMA copy of the CPU stencils (selected at run time by cpu_kernels.cpp)
 $(OBJ)/cpu/cpu_kernels_avx2.o $(ASAN_DIR)/cpu/cpu_kernels_avx2.o $(DCK_DIR)/cpu/cpu_kernels_avx2.o: HOSTFLAGS += -mavx2 -mfma

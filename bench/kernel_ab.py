@@ -88,11 +88,13 @@ def main():
         prob = m.conv9(h=nz, w=nx, dtype=a.dtype)
     elif a.kind == "star7":
         prob = m.star7(nx=nx, ny=ny, nz=nz, dtype=a.dtype)
+    elif a.kind == "star13":
+        prob = m.star13(nx=nx, ny=ny, nz=nz, dtype=a.dtype)
     else:
         prob = m.life2d(h=nz, w=nx, rule=a.rule)
     variants = [v for v in a.variants.split(";") if v]
     max_steps = max(parse_variant(v)[2] for v in variants)
-    lay = FieldLayout.make(prob, halo=max_steps)
+    lay = FieldLayout.make(prob, halo=prob.radius * max_steps)
     A = alloc_field(lay, "cuda")
     B = alloc_field(lay, "cuda")
     init_field(prob, lay, A)

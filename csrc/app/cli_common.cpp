@@ -52,9 +52,11 @@ void usage(const char* prog) {
   std::printf(
       "usage: %s [options]\n"
       "  With no size/step options the reference dialogue runs on stdin (generations, height, width).\n"
-      "  --stencil 5|7|9|27|star7|conv9|life  stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
+      "  --stencil 5|7|9|27|star7|star13|conv9|life  stencil family (5 = 2D MDF heat/Jacobi, 7 = 3D 7-pt, 27 = 3D 27-pt,\n"
       "                            9 = 2D 9-pt with --c0 --c1 --c2, default 1/3, 2/15, 1/30; star7 = 3D\n"
-      "                            7-pt with seven weights, conv9 = 2D 9-pt with nine weights, see --weights)\n"
+      "                            7-pt with seven weights, conv9 = 2D 9-pt with nine weights, see --weights;\n"
+      "                            star13 = 3D radius-2 star (4th-order Laplacian) with --c0 --c1 --c2, default\n"
+      "                            1/4, 2/15, -1/120, a frame two cells thick held, slabs only)\n"
       "  --n N | --nx --ny --nz    3D grid (N^3) ; 2D: --h ROWS --w COLS\n"
       "  --steps K (--iters, -g)   time steps / generations ; --warmup W untimed steps first\n"
       "  --dtype f32|f64           element type (life is always u8)\n"
@@ -260,10 +262,11 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     spec.dtype = kind == StencilKind::Life ? DType::U8 : dtype_from_name(o.dtype.empty() ? "f32" : o.dtype);
     spec.coef.r = o.r;
     // weights not given: the 27-point's 1/4, 1/20, 1/40; the 9-point's 1/3, 2/15, 1/30
-    const bool b9 = kind == StencilKind::Box9;
-    spec.coef.c0 = !std::isnan(o.c0) ? o.c0 : (b9 ? 1.0 / 3.0 : kind == StencilKind::Star7 ? kStar7C0 : 0.25);
-    spec.coef.c1 = !std::isnan(o.c1) ? o.c1 : (b9 ? 2.0 / 15.0 : 0.05);
-    spec.coef.c2 = !std::isnan(o.c2) ? o.c2 : (b9 ? 1.0 / 30.0 : 0.025);
+    // (the radius-2 star's 1/4, 2/15, -1/120)
+    const bool b9 = kind == StencilKind::Box9, s13 = kind == StencilKind::Star13;
+    spec.coef.c0 = !std::isnan(o.c0) ? o.c0 : (b9 ? 1.0 / 3.0 : kind == StencilKind::Star7 ? kStar7C0 : s13 ? kStar13C0 : 0.25);
+    spec.coef.c1 = !std::isnan(o.c1) ? o.c1 : (b9 ? 2.0 / 15.0 : s13 ? kStar13C1 : 0.05);
+    spec.coef.c2 = !std::isnan(o.c2) ? o.c2 : (b9 ? 1.0 / 30.0 : s13 ? kStar13C2 : 0.025);
     spec.coef.c3 = o.c3;
     // the reference dialogue reproduces the reference's arithmetic too (MDF_kernel.cu:20, D17)
     spec.coef.ref_precision = kind == StencilKind::Jacobi5 && (o.ref_precision || o.compat);
@@ -338,7 +341,7 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
       int want = hip ? hip_fused_depth(spec, g.nx) : 1;
       while (want > 1 && g.nz < 4 * (int64_t)want * nranks) want = shallower_depth(want);
       o.temporal = (hip && want > 1 &&
-                    hip_supports_steps(spec, FieldLayout::make(g, 0, g.nz, want, spec.dtype), want))
+                    hip_supports_steps(spec, FieldLayout::make(g, 0, g.nz, stencil_radius(spec.kind) * want, spec.dtype), want))
                        ? want
                        : 1;
       // (a depth one residual interval's plan never runs would only widen the halo)

@@ -81,6 +81,7 @@ const char* stencil_name(StencilKind k) {
     case StencilKind::Box27: return "box27";
     case StencilKind::Box9: return "box9";
     case StencilKind::Star7: return "star7";
+    case StencilKind::Star13: return "star13";
     case StencilKind::Conv9: return "conv9";
   }
   return "?";
@@ -93,8 +94,9 @@ StencilKind stencil_from_name(const std::string& s) {
   if (s == "box27" || s == "27" || s == "27pt") return StencilKind::Box27;
   if (s == "box9" || s == "9" || s == "9pt") return StencilKind::Box9;
   if (s == "star7" || s == "s7") return StencilKind::Star7;
+  if (s == "star13" || s == "13" || s == "s13") return StencilKind::Star13;
   if (s == "conv9" || s == "c9" || s == "3x3") return StencilKind::Conv9;
-  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|star7|conv9|life)");
+  MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|star7|star13|conv9|life)");
 }
 
 void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive) {
@@ -145,6 +147,11 @@ static bool weights_from_text(const std::string& s, double* w, int count) {
     pos = end + 1;
   }
   return ok && n == count;
+}
+
+void star13_check_weights(const StencilCoef& c) {
+  if (!std::isfinite(c.c0) || !std::isfinite(c.c1) || !std::isfinite(c.c2))
+    MDFX_FAIL("star13 weights must be finite (c0, c1, c2)");
 }
 
 void star7_weights_from_text(const std::string& s, StencilCoef& coef) {

@@ -44,13 +44,16 @@ void cpu_stencil(const StencilSpec& spec, const RegionArgs& a) {
   MDFX_CHECK(a.ly_end <= a.ly_begin || (a.ly_begin >= a.lay.hy && a.ly_end <= a.lay.hy + a.lay.nyl()),
              "row range must lie inside the owned rows");
   if (a.steps == 1) {
+    // (a slab that is the whole grid has no ghost planes to read: its faces are held)
+    MDFX_CHECK(stencil_radius(spec.kind) == 1 || a.lay.nzl() == a.lay.global.nz || a.lay.halo >= stencil_radius(spec.kind),
+               "a step on a slab needs halo >= the stencil's radius");
     cpu_region(spec, a);
     return;
   }
   // fused k-step sweep = k single steps through a scratch copy, widening the first steps by the
-  // planes the later ones read (the device kernel computes exactly these values on chip)
-  const int k = a.steps;
-  MDFX_CHECK(k >= 1 && a.lay.halo >= k, "fused steps need halo >= steps");
+  // planes the later ones read: `radius` per step (the device kernel computes exactly these values on chip)
+  const int k = a.steps, rad = stencil_radius(spec.kind);
+  MDFX_CHECK(k >= 1 && a.lay.halo >= rad * k, "fused steps need halo >= radius * steps");
   std::vector<char> tmp[2];
   tmp[0].assign(a.lay.bytes(), 0);
   tmp[1].assign(a.lay.bytes(), 0);
@@ -60,12 +63,12 @@ void cpu_stencil(const StencilSpec& spec, const RegionArgs& a) {
     RegionArgs b = a;
     b.in = tmp[(s - 1) & 1].data();
     b.out = s == k ? a.out : (void*)tmp[s & 1].data();
-    b.lz_begin = a.lz_begin - (k - s);
-    b.lz_end = a.lz_end + (k - s);
+    b.lz_begin = a.lz_begin - rad * (k - s);
+    b.lz_end = a.lz_end + rad * (k - s);
     // the rows the later steps read, as far as the layout holds them (a pencil's ghost rows;
     // global boundary rows are held, so a slab needs no widening)
-    b.ly_begin = std::max<int64_t>(yb - (k - s), a.lay.hy > 0 ? 1 : 0);
-    b.ly_end = std::min<int64_t>(ye + (k - s), a.lay.hy > 0 ? a.lay.rows() - 1 : a.lay.rows());
+    b.ly_begin = std::max<int64_t>(yb - rad * (k - s), a.lay.hy > 0 ? 1 : 0);
+    b.ly_end = std::min<int64_t>(ye + rad * (k - s), a.lay.hy > 0 ? a.lay.rows() - 1 : a.lay.rows());
     b.resid = s == k ? a.resid : nullptr;
     if (s < k) std::memcpy(tmp[s & 1].data(), tmp[(s - 1) & 1].data(), a.lay.bytes());
     cpu_region(spec, b);

@@ -213,6 +213,42 @@ void star7_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const S
   if (RES) *resid += acc;
 }
 
+// 3D radius-2 star: sm::star13, the chain the device kernels evaluate. A cell within 2 of a global face
+// is copied through, so no row or plane pointer below leaves the grid.
+template <class T, bool RES>
+void star13_cpu(const T* in, T* out, const Pl& g, int64_t lb, int64_t le, const StencilCoef& cf, double* resid) {
+  const sm::Star13W<T> w{(T)cf.c0, (T)cf.c1, (T)cf.c2};
+  double acc = 0.0;
+#pragma omp parallel for schedule(static) reduction(+ : acc) if ((le - lb) * (g.ye - g.yb) * g.nx > 262144)
+  for (int64_t lz = lb; lz < le; ++lz) {
+    const int64_t gz = lz + g.gz_off;
+    for (int64_t y = g.yb; y < g.ye; ++y) {
+      const int64_t row = lz * g.plane + y * g.pitch;
+      const T* __restrict__ c = in + row;
+      T* __restrict__ o = out + row;
+      const int64_t gy = y + g.gy_off;
+      if (gz >= 2 && gz < g.gnz - 2 && gy >= 2 && gy < g.gny - 2 && g.nx > 4) {
+        const T *__restrict__ ym1 = c - g.pitch, *__restrict__ yp1 = c + g.pitch;
+        const T *__restrict__ ym2 = c - 2 * g.pitch, *__restrict__ yp2 = c + 2 * g.pitch;
+        const T *__restrict__ zm1 = c - g.plane, *__restrict__ zp1 = c + g.plane;
+        const T *__restrict__ zm2 = c - 2 * g.plane, *__restrict__ zp2 = c + 2 * g.plane;
+        o[0] = c[0];
+        o[1] = c[1];
+#pragma omp simd
+        for (int64_t x = 2; x < g.nx - 2; ++x)
+          o[x] = sm::star13<T>(c[x], c[x - 1], c[x + 1], c[x - 2], c[x + 2], ym1[x], yp1[x], ym2[x], yp2[x], zm2[x],
+                               zm1[x], zp1[x], zp2[x], w);
+        o[g.nx - 2] = c[g.nx - 2];
+        o[g.nx - 1] = c[g.nx - 1];
+      } else {
+        std::memcpy(o, c, (size_t)g.nx * sizeof(T));
+      }
+      if (RES) acc += row_resid(o, c, g.nx);
+    }
+  }
+  if (RES) *resid += acc;
+}
+
 // CONWAY: sm::life_rule (B3/S23); otherwise sm::life_like with the spec's two masks
 template <bool RES, bool CONWAY>
 void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t le, unsigned birth, unsigned survive,
@@ -290,6 +326,12 @@ void region_t(const StencilSpec& spec, const RegionArgs& a) {
         conv9_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       else
         conv9_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      break;
+    case StencilKind::Star13:
+      if (spec.dtype == DType::F32)
+        star13_cpu<float, RES>((const float*)a.in, (float*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
+      else
+        star13_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       break;
     case StencilKind::Life:
       if (spec.conway())

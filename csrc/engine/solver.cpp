@@ -41,6 +41,10 @@ Solver::Solver(const StencilSpec& spec, Extent3 global, int nranks, std::vector<
     MDFX_CHECK(global_.ny >= 1, "bad ny");
   if (spec_.kind == StencilKind::Star7) star7_check_weights(spec_.coef);
   if (spec_.kind == StencilKind::Conv9) conv9_check_weights(spec_.coef);
+  if (spec_.kind == StencilKind::Star13) {
+    star13_check_weights(spec_.coef);
+    MDFX_CHECK(opt_.py == 1, "star13 runs on slabs only (py = 1): its radius-2 ghost rows are not exchanged between pencils");
+  }
   if (spec_.kind == StencilKind::Life) MDFX_CHECK(spec_.dtype == DType::U8, "life cells are u8");
   if (spec_.kind != StencilKind::Life)
     MDFX_CHECK(spec_.dtype == DType::F32 || spec_.dtype == DType::F64, "stencil dtype must be f32 or f64");
@@ -55,7 +59,8 @@ Solver::Solver(const StencilSpec& spec, Extent3 global, int nranks, std::vector<
     hip_set_abort(0);
     hip_clear_wait_error();
   }
-  const int halo = opt_.temporal;
+  // ghost planes (and boundary-region depth): every fused step consumes `radius` planes per side
+  const int halo = stencil_radius(spec_.kind) * opt_.temporal;
   for (size_t i = 0; i < local_ranks.size(); ++i) {
     const int r = local_ranks[i];
     MDFX_CHECK(r >= 0 && r < nranks, format("local rank %d outside [0,%d)", r, nranks));
@@ -352,7 +357,7 @@ int hip_interval_depth(const StencilSpec& spec, Extent3 g, int want, int64_t res
   if (want <= 2 || residual_every <= 0) return want;
   SweepCosts c;
   c.T = std::min(want, 16);
-  const FieldLayout lay = FieldLayout::make(g, 0, g.nz, want, spec.dtype);
+  const FieldLayout lay = FieldLayout::make(g, 0, g.nz, stencil_radius(spec.kind) * want, spec.dtype);
   for (int k = 1; k <= c.T; ++k) {
     c.cost[k] = hip_sweep_cost(spec, g.nx, k);
     c.ok[k] = k == 1 || hip_supports_steps(spec, lay, k);

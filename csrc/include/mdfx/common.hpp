@@ -53,12 +53,17 @@ enum class StencilKind : int {
   Box9 = 4,     // 2D 9-point weighted stencil (centre, edge and corner weights)
   Star7 = 5,    // 3D 7-point star with seven independent weights (anisotropy, advection, decay)
   Conv9 = 6,    // 2D 9-point stencil with nine independent weights (any 3x3 linear update)
+  Star13 = 7,   // 3D radius-2 star: the 13 points of the fourth-order Laplacian (centre, 6 at 1, 6 at 2)
 };
 const char* stencil_name(StencilKind k);
 StencilKind stencil_from_name(const std::string& s);
 inline bool stencil_is_2d(StencilKind k) {
   return k == StencilKind::Jacobi5 || k == StencilKind::Life || k == StencilKind::Box9 || k == StencilKind::Conv9;
 }
+// How far the stencil reaches along each axis. One fused step consumes `radius` ghost planes per side,
+// and the held (Dirichlet) frame is `radius` cells thick: a cell is copied through iff one of its
+// coordinates is within `radius` of a global face, so no update reads outside the grid.
+inline int stencil_radius(StencilKind k) { return k == StencilKind::Star13 ? 2 : 1; }
 
 // Coefficients. Jacobi5/Heat7: u' = u + r * (sum_neighbours - 2d * u). Box27:
 // u' = c0*u + c1*sum(6 faces) + c2*sum(12 edges) + c3*sum(8 corners). Box9:
@@ -68,7 +73,11 @@ inline bool stencil_is_2d(StencilKind k) {
 // Sum |w| <= 1 keeps the max-norm from growing. Conv9: u' = sum over dz, dx in {-1, 0, 1} of
 // w9[3*(dz+1) + (dx+1)] * u(z+dz, x+dx) (row-major; z is the row axis, x runs along the row), evaluated as
 // sm::conv9. Its default is a diffusion with a positive cross term, weights non-negative and summing to 1.
+// Star13: u' = c0*u + c1*sum(the 6 neighbours at distance 1) + c2*sum(the 6 at distance 2 along the axes),
+// evaluated as sm::star13 (c3 unused). Its defaults kStar13C0/C1/C2 are the explicit fourth-order heat step
+// u + r * Lap4(u) with r = 0.1: c0 = 1 - 7.5 r, c1 = 4 r / 3, c2 = -r / 12; they sum to 1, sum |w| = 1.1.
 constexpr double kStar7C0 = 0.30;
+constexpr double kStar13C0 = 0.25, kStar13C1 = 2.0 / 15.0, kStar13C2 = -1.0 / 120.0;
 struct StencilCoef {
   double r = -1.0;  // < 0 -> default 1/(2d) (Jacobi)
   double c0 = 0.25, c1 = 1.0 / 20.0, c2 = 1.0 / 40.0, c3 = 3.0 / 160.0;
@@ -98,6 +107,7 @@ void star7_check_weights(const StencilCoef& coef);  // every Star7 weight finite
 // east). Any other count, a non-number or a non-finite value throws an Error that names the text.
 void conv9_weights_from_text(const std::string& s, StencilCoef& coef);
 void conv9_check_weights(const StencilCoef& coef);  // every Conv9 weight finite, else an Error
+void star13_check_weights(const StencilCoef& coef);  // c0, c1, c2 finite, else an Error
 
 struct StencilSpec {
   StencilKind kind = StencilKind::Heat7;

@@ -17,13 +17,15 @@
 namespace mdfx {
 
 // One region update: out[planes lz_begin..lz_end) = stencil(in). Cells on the global boundary
-// (x, y or z equal to 0 or n-1) are Dirichlet: copied through unchanged.
+// (x, y or z within R = stencil_radius(kind) of a face: 0 or n-1 for the radius-1 kinds, also 1 and n-2
+// for star13) are Dirichlet: copied through unchanged.
 //
-// Footprint of a launch of K = steps fused steps (tests/test_gpu_footprint.py, docs/DESIGN.md section 2):
+// Footprint of a launch of K = steps fused steps of a stencil of radius R (tests/test_gpu_footprint.py,
+// docs/DESIGN.md section 2):
 //   writes: the region's planes (both regions'), columns [0, nx); the pad columns [nx, pitch) of
 //           those planes only as a copy of the input's pad; nothing else (no other owned plane,
 //           no ghost plane, no slack), and never `in`.
-//   reads:  planes [lz_begin-K, lz_end+K) for values that matter; anything else in the storage
+//   reads:  planes [lz_begin - R*K, lz_end + R*K) for values that matter; anything else in the storage
 //           (pad, ghost planes outside the global grid, planes beyond that window, the slack)
 //           only into lanes that meet held or unowned cells.
 //   caller: pad, out-of-grid ghost planes and slack are finite and of moderate magnitude (held
@@ -40,8 +42,8 @@ struct RegionArgs {
   // storage rows to write (pencil layouts: the y-boundary strips); empty = every owned row
   int64_t ly_begin = 0, ly_end = 0;
   double* resid = nullptr;           // optional accumulator of sum((out-in)^2) over the region
-  // Time steps fused into this sweep (temporal blocking). 2 needs lay.halo >= 2 and reads
-  // in[lz_begin-2, lz_end+2); the residual then covers the second step only.
+  // Time steps fused into this sweep (temporal blocking). K steps of a radius-R stencil need
+  // lay.halo >= R*K and read in[lz_begin - R*K, lz_end + R*K); the residual then covers the last step only.
   int steps = 1;
   // Minimum whole rounds of resident blocks per streaming fused sweep (0 = 1, at most 4). The engine
   // asks for 2 when slabs exchange halos: the exchange's RCCL / copy kernels then find CUs freed

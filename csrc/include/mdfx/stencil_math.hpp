@@ -115,6 +115,42 @@ MDFX_HDI T star7(T c, T xm, T xp, T ym, T yp, T zm, T zp, const Star7W<T>& w) {
   return star7_finish<T>(star7_P<T>(B, zm, w.zm), zp, w.zp);
 }
 
+// 3D radius-2 star (star13; the fourth-order Laplacian's points): a pure chain of one multiply and twelve
+// fmas, ordered for a march along z. c1 weighs the six neighbours at distance 1, c2 the six at distance 2.
+// For one cell,
+//   B  = the cell's own plane: c0 * c, then fmas of x-1, x+1 (c1), x-2, x+2 (c2), y-1, y+1 (c1), y-2, y+2 (c2)
+//   P  = fma(c1, u(z-1), fma(c2, u(z-2), B))   complete once plane z has arrived
+//   Q  = fma(c1, u(z+1), P)                    when plane z + 1 arrives
+//   u' = fma(c2, u(z+2), Q)                    finished when plane z + 2 arrives
+// so the z terms enter in the order the planes pass: z-2, z-1, z+1, z+2.
+template <class T>
+struct Star13W {
+  T c0, c1, c2;
+};
+template <class T>
+MDFX_HDI T star13_B(T c, T xm1, T xp1, T xm2, T xp2, T ym1, T yp1, T ym2, T yp2, const Star13W<T>& w) {
+  const T bx = fmaT(w.c2, xp2, fmaT(w.c2, xm2, fmaT(w.c1, xp1, fmaT(w.c1, xm1, w.c0 * c))));
+  return fmaT(w.c2, yp2, fmaT(w.c2, ym2, fmaT(w.c1, yp1, fmaT(w.c1, ym1, bx))));
+}
+template <class T>
+MDFX_HDI T star13_P(T B, T zm2, T zm1, const Star13W<T>& w) {
+  return fmaT(w.c1, zm1, fmaT(w.c2, zm2, B));
+}
+template <class T>
+MDFX_HDI T star13_zp1(T P, T zp1, const Star13W<T>& w) {
+  return fmaT(w.c1, zp1, P);
+}
+template <class T>
+MDFX_HDI T star13_zp2(T Q, T zp2, const Star13W<T>& w) {
+  return fmaT(w.c2, zp2, Q);
+}
+template <class T>
+MDFX_HDI T star13(T c, T xm1, T xp1, T xm2, T xp2, T ym1, T yp1, T ym2, T yp2, T zm2, T zm1, T zp1, T zp2,
+                  const Star13W<T>& w) {
+  const T B = star13_B<T>(c, xm1, xp1, xm2, xp2, ym1, yp1, ym2, yp2, w);
+  return star13_zp2<T>(star13_zp1<T>(star13_P<T>(B, zm2, zm1, w), zp1, w), zp2, w);
+}
+
 // 2D 9-point with nine independent weights (conv9; rows are the z axis), ordered for a march over rows.
 // w is row-major: w[3*(dz+1) + (dx+1)] multiplies u(z+dz, x+dx). An arriving row p with c = v(x),
 // l = v(x-1), r = v(x+1) yields three horizontal sums, each one multiply and two fmas:

@@ -45,6 +45,9 @@ void launch_conv9(const Geo& g, const T* in, T* out, const StencilCoef& c, int s
 // 3D 7-point star with seven weights: star7_tbk (1, 2, 3, 4 steps per sweep), stencil_star7.hip
 template <class T>
 void launch_star7(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
+// 3D radius-2 star: star13_tbk (1, 2 steps per sweep), stencil_star13.hip
+template <class T>
+void launch_star13(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
 void launch_life(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tb2(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
 void launch_life_tbk(const Geo& g, const uint8_t* in, uint8_t* out, int steps, double* resid, hipStream_t s);
@@ -259,7 +262,7 @@ void hip_init(const InitSpec& init, const FieldLayout& lay, void* buf, void* str
 
 bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int steps) {
   if (steps == 1) return true;
-  if (steps < 2 || lay.halo < steps) return false;
+  if (steps < 2 || lay.halo < stencil_radius(spec.kind) * steps) return false;
   if (lay.pencil())  // pencils (y ghost rows): the fused 7-point sweep of heat7_wxk only
     return spec.kind == StencilKind::Heat7 && dev::heat7_wxk_supported(steps) && lay.hy >= steps &&
            dev::knobs().h7_wxk != 0;
@@ -269,6 +272,7 @@ bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int ste
   if (spec.kind == StencilKind::Box9) return k2d;  // box9_tbk
   if (spec.kind == StencilKind::Conv9) return k2d;  // conv9_tbk
   if (spec.kind == StencilKind::Star7) return steps <= 4;  // star7_tbk: any nx, ny, nz
+  if (spec.kind == StencilKind::Star13) return steps == 2;  // star13_tbk: any nx, ny, nz
   // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
   if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;
   if (spec.kind == StencilKind::Heat7 && steps > 2) {  // deep temporal blocking (rows within one block)
@@ -316,6 +320,11 @@ int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
       // 552 / 266 (322 / 618 / 731 / 1011). star7_tbk's strips are 4 / 4 / 3 (fp64 2) / 1 rows (deeper
       // strips spilled), so K = 4 updates 2.5 rows per row it stores (profiles/r09_star7/)
       return 3;
+    case StencilKind::Star13:
+      // 512^3 fp32 423 / 451 GCells/s for K = 1 / 2 (heat7's kernels in the same call: 670 / 1284, star7's
+      // 563 / 882), fp64 270 / 217 (320 / 622, 294 / 471): the fp64 K = 2 sweep (strips of 3 rows, one wave
+      // per SIMD) costs 2.49 single steps and loses; fp32 K = 2 wins by 6-7 % (profiles/r11_star13/)
+      return spec.dtype == DType::F64 ? 1 : 2;
     case StencilKind::Life:
       // any other rule (life_rule_bits): 12 as well, by its own measurement. 32768^2, HighLife, GCells/s
       // for K = 1 / 2 / 3 / 4 / 6 / 8 / 12 / 16: 2232 / 4415 / 6532 / 8584 / 12656 / 16217 / 19233 / 16380
@@ -402,6 +411,11 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
     static const double f64[5] = {0.0, 1.0, 1.24, 1.60, 4.41};
     return (spec.dtype == DType::F64 ? f64 : f32)[steps];
   }
+  if (spec.kind == StencilKind::Star13 && steps == 2) {
+    // star13_tbk's K = 2 sweep against its single step at 512^3, two repeats (profiles/r11_star13/): fp32
+    // 0.2969-0.2981 ms per step against 0.3172-0.3176, fp64 0.6183-0.6190 against 0.4959-0.4965
+    return spec.dtype == DType::F64 ? 2.49 : 1.87;
+  }
   if (spec.kind == StencilKind::Life && !spec.conway() && steps <= 16 && nx >= 8192) {
     // life_rule_bits' per-sweep times against its own single step at 32768^2 (profiles/r08_life_rules/):
     // one pass over memory up to K = 8, bound by its arithmetic from K = 12 on, and K = 16 (2 waves per
@@ -435,6 +449,11 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
   if (a.lz_end <= a.lz_begin) return;
   MDFX_CHECK(a.lz_begin >= a.lay.halo && a.lz_end <= a.lay.halo + a.lay.nzl(),
              "region must lie inside the owned planes");
+  // (a slab that is the whole grid has no ghost planes to read: its faces are held)
+  MDFX_CHECK(a.steps != 1 || stencil_radius(spec.kind) == 1 || a.lay.nzl() == a.lay.global.nz ||
+                 a.lay.halo >= stencil_radius(spec.kind),
+             format("a %s step on a slab reads %d ghost planes per side (halo %d)", stencil_name(spec.kind),
+                    stencil_radius(spec.kind), a.lay.halo));
   dev::Geo g = dev::make_geo(a.lay, a.lz_begin, a.lz_end);
   g.lz2_begin = a.lz2_begin;
   g.lz2_end = a.lz2_end;
@@ -501,6 +520,11 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
         dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
       else
         dev::launch_star7<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
+    } else if (spec.kind == StencilKind::Star13) {
+      if (spec.dtype == DType::F32)
+        dev::launch_star13<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
+      else
+        dev::launch_star13<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
     } else if (spec.kind == StencilKind::Life && !spec.conway()) {
       dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, a.steps,
                             a.resid, s);
@@ -592,6 +616,12 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
           dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
         else
           dev::launch_star7<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
+        break;
+      case StencilKind::Star13:
+        if (spec.dtype == DType::F32)
+          dev::launch_star13<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
+        else
+          dev::launch_star13<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
         break;
       case StencilKind::Life:
         if (spec.conway())

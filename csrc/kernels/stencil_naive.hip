@@ -173,6 +173,8 @@ template <class T>
 void launch_box9_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
 template <class T>
 void launch_star7_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
+template <class T>
+void launch_star13_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
 
 static int naive_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
@@ -235,6 +237,12 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
         for (int i = 0; i < 9; ++i) k.w[i] = spec.coef.w9[i];
         MDFX_NAIVE(naive_conv9, double, k);
       }
+      break;
+    case StencilKind::Star13:  // (stencil_star13.hip, for the same reason)
+      if (spec.dtype == DType::F32)
+        launch_star13_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
+      else
+        launch_star13_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
       break;
     case StencilKind::Life: {
       const TableRule tr{spec.coef.birth, spec.coef.survive};

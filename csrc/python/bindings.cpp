@@ -112,6 +112,7 @@ StencilSpec make_spec(const std::string& kind, const std::string& dtype, double 
   if (w9.size() != 9) throw Error(format("w9 takes nine weights, row-major (got %d)", (int)w9.size()));
   std::copy(w9.begin(), w9.end(), s.coef.w9);
   if (s.kind == StencilKind::Conv9) conv9_check_weights(s.coef);
+  if (s.kind == StencilKind::Star13) star13_check_weights(s.coef);
   return s;
 }
 

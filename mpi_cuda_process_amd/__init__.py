@@ -13,7 +13,7 @@ Entry points: :class:`Simulation` (decomposed, multi-slab / multi-GPU runs), :fu
 
 Layout::
 
-    models/    problem families (mdf2d, life2d, heat3d, box27, box9, star7, conv9)
+    models/    problem families (mdf2d, life2d, heat3d, box27, box9, star7, conv9, star13)
     ops/       torch-facing kernel ops + plain-PyTorch reference stencils
     parallel/  slab decomposition, torch.distributed bootstrap, torch p2p transport
     utils/     metrics, ASCII output, CLI helpers
@@ -51,10 +51,10 @@ else:
 
 from ._native import hip_available, native, require_hip  # noqa: F401,E402  (imports torch first)
 from .engine import Simulation  # noqa: F401
-from .models import InitCondition, Problem, box9, box27, conv9, from_name, heat3d, life2d, mdf2d, star7  # noqa: F401
+from .models import InitCondition, Problem, box9, box27, conv9, from_name, heat3d, life2d, mdf2d, star7, star13  # noqa: F401
 from .ops import advance  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["Simulation", "Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "conv9", "from_name",
+__all__ = ["Simulation", "Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "conv9", "star13", "from_name",
            "advance", "native", "hip_available", "require_hip"]

@@ -21,7 +21,7 @@ from .utils import metrics_record, print_array
 
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m mpi_cuda_process_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("--stencil", default="7", help="5 | 7 | 9 | 27 | star7 | conv9 | life (aliases: mdf, heat7, box9, box27, s7, c9, 3x3, gol)")
+    p.add_argument("--stencil", default="7", help="5 | 7 | 9 | 27 | star7 | star13 | conv9 | life (aliases: mdf, heat7, box9, box27, s7, 13, s13, c9, 3x3, gol)")
     p.add_argument("--n", type=int, default=0)
     p.add_argument("--nx", type=int, default=0)
     p.add_argument("--ny", type=int, default=0)

@@ -55,7 +55,7 @@ def auto_temporal(problem: Problem, nranks: int, device: str, py: int = 1, resid
     while want > 1 and problem.nz < 4 * want * nranks:
         want = {5: 4, 3: 2}.get(want, want // 2)
     if want > 1 and native().hip_supports_steps(problem.kind, problem.dtype, problem.nx, problem.ny, problem.nz,
-                                                want, want, problem.ref_precision):
+                                                problem.radius * want, want, problem.ref_precision):
         # the depth for the residual interval (native interval_depth: least plan cost on one rank,
         # whole sweeps of the depth with several)
         return native().hip_auto_depth(problem.kind, problem.dtype, problem.nx, problem.ny, problem.nz, want,
@@ -73,7 +73,7 @@ class Simulation:
     planes + exchange; ``sync_debug`` serialise every phase (race screen); ``residual_every`` k:
     global L2 norm of the update every k steps (NaN/Inf guard); ``graph`` replay two-sweep cycles
     as hipGraphs; ``timeout_s`` watchdog; ``temporal`` fused steps per sweep (1 = none, 0 = auto,
-    see :func:`auto_temporal`; halo planes = temporal); ``share_gpu`` let several engine processes
+    see :func:`auto_temporal`; halo planes = temporal x the stencil's radius); ``share_gpu`` let several engine processes
     use one GPU with the ipc transport (tests only: its device spin waits assume one process per
     GPU, native ipc_shared_gpu_problem).
     """

@@ -15,6 +15,8 @@ the default initial condition. Families (reference parity in brackets):
   constant-velocity advection-diffusion, decay), Dirichlet faces
 * :func:`conv9`   — 2D 9-point stencil with nine independent weights (any 3x3 linear update: upwind
   advection-diffusion, anisotropic conductivities, a full diffusion tensor, blur, sharpening), Dirichlet edges
+* :func:`star13`  — 3D radius-2 star, the 13 points of the fourth-order Laplacian (seismic, wave and
+  high-accuracy diffusion codes); the held frame is two cells thick
 
 2D grids are stored as ``nx = w, ny = 1, nz = h``: rows are the slab axis, exactly like the
 reference's row split (MDF_kernel.cu:30,54).
@@ -25,7 +27,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field, replace
 from typing import Optional
 
-KINDS = ("jacobi5", "life", "heat7", "box27", "box9", "star7", "conv9")
+KINDS = ("jacobi5", "life", "heat7", "box27", "box9", "star7", "conv9", "star13")
 KINDS_2D = ("jacobi5", "life", "box9", "conv9")
 
 # the default weights of conv9, row-major: a diffusion with a positive cross term; non-negative, summing to 1
@@ -101,6 +103,12 @@ class Problem:
     @property
     def dims(self) -> int:
         return 2 if self.kind in KINDS_2D else 3
+
+    @property
+    def radius(self) -> int:
+        """How far the stencil reaches along each axis: ghost planes per fused step, and the thickness
+        of the held frame."""
+        return 2 if self.kind == "star13" else 1
 
     @property
     def cells(self) -> int:
@@ -202,16 +210,33 @@ def conv9(h: int = 256, w: int = 256, dtype: str = "f32", w9=CONV9_DEFAULT,
                    init=init or InitCondition(kind="dirichlet", edge=100.0, interior=0.0))
 
 
+def star13(n: int = 256, nx: Optional[int] = None, ny: Optional[int] = None, nz: Optional[int] = None,
+           dtype: str = "f32", c0: Optional[float] = None, c1: Optional[float] = None, c2: Optional[float] = None,
+           r: Optional[float] = None, init: Optional[InitCondition] = None) -> Problem:
+    """3D radius-2 star u' = c0 u + c1 (the 6 neighbours at distance 1) + c2 (the 6 at distance 2 along the
+    axes) on an nx x ny x nz grid (default n^3). ``r`` sets the explicit fourth-order heat step
+    u + r Lap4(u): c0 = 1 - 7.5 r, c1 = 4 r / 3, c2 = -r / 12 (the default is r = 0.1: weights summing to 1,
+    sum |w| = 1.1); ``c0, c1, c2`` given explicitly win over it. Weights must be finite.
+
+    A cell is held (copied through) iff one of its coordinates is within 2 of a face, so no update reads
+    outside the grid, and a grid with an extent below 5 never changes. The ``dirichlet`` initial condition
+    still paints a one-cell frame: the second layer is held at its interior value."""
+    r = 0.1 if r is None else r
+    return Problem("star13", nx=nx or n, ny=ny or n, nz=nz or n, dtype=dtype,
+                   c0=1.0 - 7.5 * r if c0 is None else c0, c1=4.0 * r / 3.0 if c1 is None else c1,
+                   c2=-r / 12.0 if c2 is None else c2, init=init or InitCondition(kind="random", seed=1))
+
+
 def from_name(kind: str, **kw) -> Problem:
     aliases = {"5": "jacobi5", "mdf": "jacobi5", "jacobi5": "jacobi5", "life": "life", "gol": "life",
                "7": "heat7", "heat7": "heat7", "jacobi7": "heat7", "27": "box27", "box27": "box27",
                "9": "box9", "9pt": "box9", "box9": "box9", "star7": "star7", "s7": "star7",
-               "conv9": "conv9", "c9": "conv9", "3x3": "conv9"}
+               "conv9": "conv9", "c9": "conv9", "3x3": "conv9", "star13": "star13", "13": "star13", "s13": "star13"}
     k = aliases.get(str(kind))
     if k is None:
         raise ValueError("unknown stencil %r" % kind)
     return {"jacobi5": mdf2d, "life": life2d, "heat7": heat3d, "box27": box27, "box9": box9,
-            "star7": star7, "conv9": conv9}[k](**kw)
+            "star7": star7, "conv9": conv9, "star13": star13}[k](**kw)
 
 
-__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "conv9", "from_name", "KINDS"]
+__all__ = ["Problem", "InitCondition", "mdf2d", "life2d", "heat3d", "box27", "box9", "star7", "conv9", "star13", "from_name", "KINDS"]

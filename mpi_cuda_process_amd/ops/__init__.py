@@ -88,14 +88,14 @@ def apply_stencil(problem: Problem, layout: FieldLayout, src: torch.Tensor, dst:
 
     ``resid`` (float64 scalar tensor on the same device), when given, accumulates
     sum((dst - src)^2) over the region. ``steps`` > 1 fuses that many time steps into one sweep
-    (temporal blocking; needs ``layout.halo >= steps`` and valid ghosts that deep); the residual
+    (temporal blocking; needs ``layout.halo >= problem.radius * steps`` and valid ghosts that deep); the residual
     then covers the last step. ``second`` = (lz_begin, lz_end) of a second region updated by the
     same call (the engine's pair of boundary regions; one launch for the fused 3D 7-point sweep).
 
     Footprint (``RegionArgs`` in kernels.hpp; tests/test_gpu_footprint.py): the call writes the
     regions' planes, columns ``[0, nx)``, and the pad columns of those planes only as a copy of
     ``src``'s pad; it writes nothing else in ``dst`` and never ``src``. It reads planes
-    ``[lz_begin - steps, lz_end + steps)`` for values that matter and anything else in the storage
+    ``[lz_begin - radius * steps, lz_end + radius * steps)`` for values that matter and anything else in the storage
     only into lanes that meet held or unowned cells. The caller provides pad columns, ghost planes
     outside the global grid and slack that are finite and of moderate magnitude
     (:func:`alloc_field` zero-fills them; :func:`init_field` and the engine only ever write zero there).
@@ -169,10 +169,10 @@ def advance(problem: Problem, grid: torch.Tensor, steps: int, temporal: int = 0)
             want = 2 if want == 3 else want // 2
         temporal = 1
         if dev.type == "cuda" and want > 1 and native().hip_supports_steps(problem.kind, problem.dtype, problem.nx,
-                                                                         problem.ny, problem.nz, want, want,
+                                                                         problem.ny, problem.nz, problem.radius * want, want,
                                                                          problem.ref_precision):
             temporal = want
-    lay = FieldLayout.make(problem, halo=max(1, temporal))
+    lay = FieldLayout.make(problem, halo=problem.radius * max(1, temporal))
     a = alloc_field(lay, dev)
     b = alloc_field(lay, dev)
     dense_to_field(problem, g.to(TORCH_DTYPE[lay.dtype]), lay, a)

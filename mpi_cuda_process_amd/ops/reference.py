@@ -96,6 +96,21 @@ def conv9(u: torch.Tensor, w9=(0.06, 0.10, 0.02, 0.14, 0.36, 0.14, 0.02, 0.10, 0
     return out if squeeze else out.unsqueeze(1)
 
 
+def star13(u: torch.Tensor, c0: float = 0.25, c1: float = 2.0 / 15.0, c2: float = -1.0 / 120.0) -> torch.Tensor:
+    """3D radius-2 star (fourth-order Laplacian points); ``u`` is (nz, ny, nx), any dtype. Cells within 2 of
+    a face are held."""
+    out = u.clone()
+    if min(u.shape) < 5:
+        return out
+    c = u[2:-2, 2:-2, 2:-2]
+    near = (u[2:-2, 2:-2, 1:-3] + u[2:-2, 2:-2, 3:-1] + u[2:-2, 1:-3, 2:-2] + u[2:-2, 3:-1, 2:-2]
+            + u[1:-3, 2:-2, 2:-2] + u[3:-1, 2:-2, 2:-2])
+    far = (u[2:-2, 2:-2, :-4] + u[2:-2, 2:-2, 4:] + u[2:-2, :-4, 2:-2] + u[2:-2, 4:, 2:-2]
+           + u[:-4, 2:-2, 2:-2] + u[4:, 2:-2, 2:-2])
+    out[2:-2, 2:-2, 2:-2] = c0 * c + c1 * near + c2 * far
+    return out
+
+
 def life(u: torch.Tensor, rule: str = "B3/S23") -> torch.Tensor:
     """Game of Life with a held (dead) frame, Conway's B3/S23 or any Life-like ``rule``; ``u`` is
     (h, 1, w) or (h, w) uint8. Integer arithmetic: the neighbour count, then a lookup in the rule's
@@ -138,6 +153,8 @@ def step(kind: str, u: torch.Tensor, **coef) -> torch.Tensor:
                      coef.get("wyp", 0.10), coef.get("wzm", 0.05), coef.get("wzp", 0.05))
     if kind == "conv9":
         return conv9(u, **({"w9": coef["w9"]} if "w9" in coef else {}))
+    if kind == "star13":
+        return star13(u, coef.get("c0", 0.25), coef.get("c1", 2.0 / 15.0), coef.get("c2", -1.0 / 120.0))
     if kind == "life":
         return life(u, coef.get("rule", "B3/S23"))
     raise ValueError(kind)
