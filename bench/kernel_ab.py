@@ -67,7 +67,9 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--variants", default="FAM=naive;RY=4,PF=2")
-    p.add_argument("--rule", default="B3/S23", help="--kind life: the Life-like rule (a variant's RULE= overrides it)")
+    p.add_argument("--rule", default="B3/S23", help="--kind life: the Life-like or Generations (B/S/C) rule "
+                                                     "(a variant's RULE= overrides it)")
+    p.add_argument("--density", type=float, default=0.15, help="--kind life: share of live cells in the initial grid")
     p.add_argument("--json", default="")
     p.add_argument("--thief", type=int, default=0,
                    help="launch this many single-block spin kernels (torch.cuda._sleep, ~--thief-us) on "
@@ -91,7 +93,7 @@ def main():
     elif a.kind == "star13":
         prob = m.star13(nx=nx, ny=ny, nz=nz, dtype=a.dtype)
     else:
-        prob = m.life2d(h=nz, w=nx, rule=a.rule)
+        prob = m.life2d(h=nz, w=nx, rule=a.rule, density=a.density)
     variants = [v for v in a.variants.split(";") if v]
     max_steps = max(parse_variant(v)[2] for v in variants)
     lay = FieldLayout.make(prob, halo=prob.radius * max_steps)

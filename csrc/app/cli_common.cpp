@@ -78,7 +78,9 @@ void usage(const char* prog) {
       "  --ref-precision           2D MDF: the reference's fp32-sum / fp64-scale evaluation of the update\n"
       "                            (default in the reference dialogue; single-step sweeps)\n"
       "  --rule B<n..>/S<n..>      Life: any outer-totalistic Moore rule, e.g. B36/S23 (HighLife),\n"
-      "                            B3678/S34678 (Day & Night), B2/S (Seeds); default B3/S23\n"
+      "                            B3678/S34678 (Day & Night), B2/S (Seeds); default B3/S23;\n"
+      "                            B<n..>/S<n..>/C<2..256>: a Generations rule with C cell states,\n"
+      "                            e.g. B2/S/C3 (Brian's Brain), B2/S345/C4 (Star Wars)\n"
       "  --residual-every K        global L2 norm of the update every K steps\n"
       "  --checkpoint-every K --checkpoint-dir D ; --resume D\n"
       "  --print                   dump the final grid like the reference's print_array\n"
@@ -279,7 +281,7 @@ int run_cli(int argc, char** argv, const char* default_stencil, const char* prog
     }
     if (!o.rule.empty()) {
       MDFX_CHECK(kind == StencilKind::Life, "--rule goes with --stencil life");
-      life_rule_from_name(o.rule, spec.coef.birth, spec.coef.survive);
+      life_rule_from_name(o.rule, spec.coef);
     }
     hip_set_kernel_variant(o.variant.c_str());
 

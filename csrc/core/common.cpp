@@ -99,8 +99,10 @@ StencilKind stencil_from_name(const std::string& s) {
   MDFX_FAIL("unknown stencil '" + s + "' (5|7|9|27|star7|star13|conv9|life)");
 }
 
-void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive) {
-  const auto bad = [&]() { MDFX_FAIL("bad Life rule '" + s + "' (B<digits 0-8>/S<digits 0-8>, e.g. B36/S23)"); };
+void life_rule_from_name(const std::string& s, StencilCoef& coef) {
+  const auto bad = [&]() {
+    MDFX_FAIL("bad Life rule '" + s + "' (B<digits 0-8>/S<digits 0-8>[/C<states 2-256>], e.g. B36/S23, B2/S345/C4)");
+  };
   uint32_t m[2] = {0, 0};
   size_t i = 0;
   for (int side = 0; side < 2; ++side) {
@@ -111,18 +113,35 @@ void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& surviv
       ++i;
     }
   }
-  if (i != s.size()) bad();
-  birth = m[0];
-  survive = m[1];
+  int states = 2;
+  if (i < s.size()) {  // "/C<n>"
+    if (s[i] != '/' || i + 1 >= s.size() || (s[i + 1] | 0x20) != 'c') bad();
+    const size_t first = i + 2;
+    states = 0;
+    for (i = first; i < s.size() && s[i] >= '0' && s[i] <= '9' && i < first + 3; ++i) states = states * 10 + (s[i] - '0');
+    if (i == first || i != s.size() || states < 2 || states > 256) bad();
+  }
+  coef.birth = m[0];
+  coef.survive = m[1];
+  coef.states = states;
 }
 
-std::string life_rule_name(uint32_t birth, uint32_t survive) {
+void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive) {
+  StencilCoef c;
+  life_rule_from_name(s, c);
+  if (c.states > 2) MDFX_FAIL("bad Life rule '" + s + "': a rule of two masks has two states, not " + std::to_string(c.states));
+  birth = c.birth;
+  survive = c.survive;
+}
+
+std::string life_rule_name(uint32_t birth, uint32_t survive, int states) {
   std::string s = "B";
   for (int n = 0; n <= 8; ++n)
     if (birth >> n & 1u) s += (char)('0' + n);
   s += "/S";
   for (int n = 0; n <= 8; ++n)
     if (survive >> n & 1u) s += (char)('0' + n);
+  if (states > 2) s += "/C" + std::to_string(states);
   return s;
 }
 

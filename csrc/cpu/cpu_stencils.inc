@@ -281,6 +281,37 @@ void life_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t 
   if (RES) *resid += acc;
 }
 
+// a Generations rule (states > 2): only the cells in state 1 are counted, sm::life_gen decides
+template <bool RES>
+void life_gen_cpu(const uint8_t* in, uint8_t* out, const Pl& g, int64_t lb, int64_t le, unsigned birth,
+                  unsigned survive, unsigned states, double* resid) {
+  double acc = 0.0;
+#pragma omp parallel for schedule(static) reduction(+ : acc) if ((le - lb) * g.nx > 1048576)
+  for (int64_t lz = lb; lz < le; ++lz) {
+    const int64_t gz = lz + g.gz_off;
+    const uint8_t* __restrict__ c = in + lz * g.plane;
+    uint8_t* __restrict__ o = out + lz * g.plane;
+    if (gz > 0 && gz < g.gnz - 1 && g.nx > 2) {
+      const uint8_t *__restrict__ zm = c - g.plane, *__restrict__ zp = c + g.plane;
+      o[0] = c[0];
+      for (int64_t x = 1; x < g.nx - 1; ++x) {
+        const unsigned n = (unsigned)(zm[x - 1] == 1) + (zm[x] == 1) + (zm[x + 1] == 1) + (c[x - 1] == 1) +
+                           (c[x + 1] == 1) + (zp[x - 1] == 1) + (zp[x] == 1) + (zp[x + 1] == 1);
+        o[x] = sm::life_gen(n, c[x], birth, survive, states);
+      }
+      o[g.nx - 1] = c[g.nx - 1];
+    } else {
+      std::memcpy(o, c, (size_t)g.nx);
+    }
+    if (RES) {
+      int64_t n = 0;
+      for (int64_t x = 0; x < g.nx; ++x) n += o[x] != c[x];
+      acc += (double)n;
+    }
+  }
+  if (RES) *resid += acc;
+}
+
 template <bool RES>
 void region_t(const StencilSpec& spec, const RegionArgs& a) {
   Pl g = pl_of(a.lay);
@@ -334,7 +365,10 @@ void region_t(const StencilSpec& spec, const RegionArgs& a) {
         star13_cpu<double, RES>((const double*)a.in, (double*)a.out, g, a.lz_begin, a.lz_end, spec.coef, a.resid);
       break;
     case StencilKind::Life:
-      if (spec.conway())
+      if (spec.generations())
+        life_gen_cpu<RES>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, spec.coef.birth,
+                          spec.coef.survive, (unsigned)spec.coef.states, a.resid);
+      else if (spec.conway())
         life_cpu<RES, true>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, 0, 0, a.resid);
       else
         life_cpu<RES, false>((const uint8_t*)a.in, (uint8_t*)a.out, g, a.lz_begin, a.lz_end, spec.coef.birth,

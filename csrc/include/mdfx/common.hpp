@@ -91,12 +91,20 @@ struct StencilCoef {
   // with n live neighbours becomes alive; bit n of `survive` set: a live cell with n live neighbours
   // stays alive. The default is Conway's B3/S23.
   uint32_t birth = 0x008, survive = 0x00C;
+  // Life only: the number of cell states C of a Generations rule (B/S/C), 2 .. 256. State 0 is dead, 1
+  // alive, 2 .. C-1 dying; only state 1 counts as a neighbour. A live cell that does not survive
+  // becomes 2 % C, a dying cell (s + 1) % C. 2 is a plain Life-like rule.
+  int states = 2;
 };
 
 // A Life-like rule in B/S notation: "B36/S23", case-insensitive, digits 0..8 in any order, either
-// side may be empty ("B2/S"). Anything else throws an Error that names the text.
+// side may be empty ("B2/S"); optionally a Generations rule "B2/S345/C4" with a decimal state count
+// 2 .. 256. Anything else throws an Error that names the text. The two-mask form takes two-state
+// rules only ("/C2" included) and throws on more states.
+void life_rule_from_name(const std::string& s, StencilCoef& coef);
 void life_rule_from_name(const std::string& s, uint32_t& birth, uint32_t& survive);
-std::string life_rule_name(uint32_t birth, uint32_t survive);  // canonical form, digits ascending
+// canonical form, digits ascending; "/C<states>" appended when states > 2
+std::string life_rule_name(uint32_t birth, uint32_t survive, int states = 2);
 
 // Star7 weights as text: "c0,xm,xp,ym,yp,zm,zp", seven comma-separated finite numbers. Any other count,
 // a non-number or a non-finite value throws an Error that names the text.
@@ -114,8 +122,10 @@ struct StencilSpec {
   DType dtype = DType::F32;
   StencilCoef coef;
   // Conway's rule runs the B3/S23 kernels (life_wave, life_tb2, life_bits, sm::life_rule); every
-  // other rule runs the table-driven ones (life_rule_bits, sm::life_like)
-  bool conway() const { return coef.birth == 0x008u && coef.survive == 0x00Cu; }
+  // other two-state rule runs the table-driven ones (life_rule_bits, sm::life_like), and a rule
+  // with more states the Generations ones (life_gen_bits, sm::life_gen)
+  bool conway() const { return coef.birth == 0x008u && coef.survive == 0x00Cu && coef.states == 2; }
+  bool generations() const { return coef.states > 2; }
   double rate() const {  // effective r for 5/7-pt
     if (coef.r >= 0) return coef.r;
     return kind == StencilKind::Jacobi5 ? 0.25 : 1.0 / 6.0;

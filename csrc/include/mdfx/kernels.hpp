@@ -74,6 +74,9 @@ struct RegionArgs {
 bool hip_region_signals(const StencilSpec& spec, const FieldLayout& lay, int steps);
 
 // Whether a fused multi-step sweep is implemented for this stencil / grid on the device.
+// Life with a Generations rule (StencilCoef::states = C > 2): cells hold 0 .. C-1, and an input cell
+// >= C is the caller's error with an unspecified result (no fault). C = 3 .. 32 runs life_gen_bits at
+// steps 1, 2, 3, 4, 6, 8; C > 32 has the naive single step only, so this returns false for steps > 1.
 bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int steps);
 // The deepest fused sweep that is a measured win for this stencil at row width nx (before any
 // cap by slab depth): 8 for the 2D MDF, 12 for Life, 4 for the 3D 7-point where heat7_wxk's x

@@ -191,5 +191,14 @@ MDFX_HDI unsigned char life_like(unsigned t, unsigned char alive, unsigned birth
   return (unsigned char)(((a ? survive : birth) >> (t - a)) & 1u);
 }
 
+// A Generations rule (B/S/C) with `states` = C cell states, 2 .. 256: n is the number of the eight
+// neighbours whose state is exactly 1; s the cell's own state (0 dead, 1 alive, 2 .. C-1 dying).
+// life_gen(n, s, b, v, 2) == life_like(n + s, s, b, v) for s in {0, 1}.
+MDFX_HDI unsigned char life_gen(unsigned n, unsigned char s, unsigned birth, unsigned survive, unsigned states) {
+  if (s == 0) return (unsigned char)((birth >> n) & 1u);
+  if (s == 1) return (unsigned char)(((survive >> n) & 1u) ? 1u : 2u % states);
+  return (unsigned char)((s + 1u) % states);
+}
+
 }  // namespace sm
 }  // namespace mdfx

@@ -54,6 +54,10 @@ void launch_life_tbk(const Geo& g, const uint8_t* in, uint8_t* out, int steps, d
 // any rule but Conway's: life_rule_bits (1, 2, 3, 4, 6, 8, 12, 16 generations), stencil_life_rule.hip
 void launch_life_rule(const Geo& g, const uint8_t* in, uint8_t* out, uint32_t birth, uint32_t survive, int steps,
                       double* resid, hipStream_t s);
+// a Generations rule with 3 .. 32 states: life_gen_bits (1, 2, 3, 4, 6, 8 generations), stencil_life_gen.hip
+void launch_life_gen(const Geo& g, const uint8_t* in, uint8_t* out, uint32_t birth, uint32_t survive, int states,
+                     int steps, double* resid, hipStream_t s);
+bool life_gen_supported(int states, int steps);
 template <class T>
 void launch_heat7_tb2(const Geo& g, const T* in, T* out, T r, double* resid, hipStream_t s);
 template <class T>
@@ -273,6 +277,8 @@ bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int ste
   if (spec.kind == StencilKind::Conv9) return k2d;  // conv9_tbk
   if (spec.kind == StencilKind::Star7) return steps <= 4;  // star7_tbk: any nx, ny, nz
   if (spec.kind == StencilKind::Star13) return steps == 2;  // star13_tbk: any nx, ny, nz
+  // a Generations rule: life_gen_bits' depths for 3 .. 32 states; more states have the naive single step only
+  if (spec.kind == StencilKind::Life && spec.generations()) return dev::life_gen_supported(spec.coef.states, steps);
   // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
   if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;
   if (spec.kind == StencilKind::Heat7 && steps > 2) {  // deep temporal blocking (rows within one block)
@@ -296,6 +302,26 @@ bool hip_region_signals(const StencilSpec& spec, const FieldLayout& lay, int ste
   return !lay.pencil() && spec.kind == StencilKind::Heat7 &&
          (steps == 3 || steps == 4 || steps == 5) && lay.halo >= steps &&
          dev::use_wtk(steps, spec.dtype) && dev::use_wxk(spec.dtype, lay.global.nx, steps);
+}
+
+// Generations rules (life_gen_bits, 3 .. 32 states in P = 2 .. 5 bit planes). 32768^2, density 0.5, GCells/s
+// for K = 1 / 2 / 3 / 4 / 6 / 8, alternating in one process with life_rule_bits (HighLife: 2254 / 4461 /
+// 6596 / 8679 / 12721 / 16262), best of 5 rounds of 100 sweeps, two runs within 0.5 % (profiles/r12_life_generations/):
+//   C = 3  (P = 2)  2160 / 4238 / 6415 / 8577 / 12288 / 14581      C = 16 (P = 4)  2106 / 4288 / 6349 / 8022 / 9707 / 10257
+//   C = 8  (P = 3)  2138 / 4213 / 6407 / 8478 / 11260 / 11794      C = 32 (P = 5)  2089 / 4212 / 5890 / 6948 / 8208 / 8983
+// The deepest built sweep is the fastest per generation at every P; the naive kernel runs C = 3 at 394. More
+// than 32 states have the naive single step only.
+static int life_gen_depth(int states) { return states <= 32 ? 8 : 1; }
+// per-sweep times against the same P's single step in that run: one pass over memory up to K = 6 / 4 / 4 / 2
+// for P = 2 / 3 / 4 / 5, bound by the arithmetic (4 P + 3 ops per generation on top of life_rule_bits' 32) beyond
+static double life_gen_cost(int states, int steps) {
+  static const double c[4][9] = {{0.0, 1.0, 1.02, 1.01, 1.01, 0.0, 1.05, 0.0, 1.18},
+                                 {0.0, 1.0, 1.02, 1.00, 1.01, 0.0, 1.14, 0.0, 1.45},
+                                 {0.0, 1.0, 0.98, 1.00, 1.05, 0.0, 1.30, 0.0, 1.64},
+                                 {0.0, 1.0, 0.99, 1.06, 1.20, 0.0, 1.53, 0.0, 1.86}};
+  const int p = states <= 4 ? 0 : states <= 8 ? 1 : states <= 16 ? 2 : 3;
+  if (states <= 32 && steps <= 8 && c[p][steps] > 0.0) return c[p][steps];
+  return 1.0 + 0.05 * (steps - 1);
 }
 
 int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
@@ -330,6 +356,7 @@ int hip_fused_depth(const StencilSpec& spec, int64_t nx) {
       // for K = 1 / 2 / 3 / 4 / 6 / 8 / 12 / 16: 2232 / 4415 / 6532 / 8584 / 12656 / 16217 / 19233 / 16380
       // (Conway's kernels in the same call: 2438 / 4842 / 6329 / 8310 / 12157 / 16280 / 22639 / 22286);
       // K = 16 runs at 2 waves per SIMD (177-184 VGPRs) and loses (profiles/r08_life_rules/)
+      if (spec.generations()) return life_gen_depth(spec.coef.states);
       return 12;
     case StencilKind::Box27:
       // K = 3 through box27_wxk for fp64 (512^3: 663 vs 527 GCells/s for box27_tbk K = 2), for fp32
@@ -416,6 +443,7 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
     // 0.2969-0.2981 ms per step against 0.3172-0.3176, fp64 0.6183-0.6190 against 0.4959-0.4965
     return spec.dtype == DType::F64 ? 2.49 : 1.87;
   }
+  if (spec.kind == StencilKind::Life && spec.generations() && nx >= 8192) return life_gen_cost(spec.coef.states, steps);
   if (spec.kind == StencilKind::Life && !spec.conway() && steps <= 16 && nx >= 8192) {
     // life_rule_bits' per-sweep times against its own single step at 32768^2 (profiles/r08_life_rules/):
     // one pass over memory up to K = 8, bound by its arithmetic from K = 12 on, and K = 16 (2 waves per
@@ -525,6 +553,9 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
         dev::launch_star13<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
       else
         dev::launch_star13<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
+    } else if (spec.kind == StencilKind::Life && spec.generations()) {
+      dev::launch_life_gen(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive,
+                           spec.coef.states, a.steps, a.resid, s);
     } else if (spec.kind == StencilKind::Life && !spec.conway()) {
       dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, a.steps,
                             a.resid, s);
@@ -624,7 +655,12 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
           dev::launch_star13<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
         break;
       case StencilKind::Life:
-        if (spec.conway())
+        if (spec.generations() && dev::life_gen_supported(spec.coef.states, 1))
+          dev::launch_life_gen(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive,
+                               spec.coef.states, 1, a.resid, s);
+        else if (spec.generations())  // more than 32 states
+          dev::naive_launch(spec, g, a.in, a.out, a.resid, s);
+        else if (spec.conway())
           dev::launch_life(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.resid, s);
         else
           dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, 1,

@@ -132,13 +132,24 @@ __global__ __launch_bounds__(256) void naive_conv9(const T* __restrict__ in, T* 
 
 // the rule of a Life kernel: Conway's fixed compare (sm::life_rule) or the two masks of any other
 // outer-totalistic rule (sm::life_like); passed last, so Conway's kernel arguments stay where they were
+// (term: what a cell of the 3x3 block adds to t)
 struct ConwayRule {
+  __device__ unsigned term(unsigned char v) const { return v; }
   __device__ unsigned char operator()(unsigned t, unsigned char c) const { return sm::life_rule(t, c); }
 };
 struct TableRule {
   unsigned birth, survive;
+  __device__ unsigned term(unsigned char v) const { return v; }
   __device__ unsigned char operator()(unsigned t, unsigned char c) const {
     return sm::life_like(t, c, birth, survive);
+  }
+};
+// a Generations rule (sm::life_gen), 3 .. 256 states: only cells in state 1 count
+struct GenRule {
+  unsigned birth, survive, states;
+  __device__ unsigned term(unsigned char v) const { return v == 1; }
+  __device__ unsigned char operator()(unsigned t, unsigned char c) const {
+    return sm::life_gen(t - (c == 1), c, birth, survive, states);
   }
 };
 
@@ -160,7 +171,7 @@ __global__ __launch_bounds__(256) void naive_life(const uint8_t* __restrict__ in
 #pragma unroll
       for (int dz = -1; dz <= 1; ++dz)
 #pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) t += in[idx + dz * g.plane + dx];
+        for (int dx = -1; dx <= 1; ++dx) t += rule.term(in[idx + dz * g.plane + dx]);
       o = rule(t, c);
     }
     out[idx] = o;
@@ -246,7 +257,12 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
       break;
     case StencilKind::Life: {
       const TableRule tr{spec.coef.birth, spec.coef.survive};
-      if (spec.conway() && res)
+      const GenRule gr{spec.coef.birth, spec.coef.survive, (unsigned)spec.coef.states};
+      if (spec.generations() && res)
+        hipLaunchKernelGGL((naive_life<true, GenRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid, gr);
+      else if (spec.generations())
+        hipLaunchKernelGGL((naive_life<false, GenRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid, gr);
+      else if (spec.conway() && res)
         hipLaunchKernelGGL((naive_life<true, ConwayRule>), grd, blk, 0, s, (const uint8_t*)in, (uint8_t*)out, g, resid,
                            ConwayRule{});
       else if (spec.conway())

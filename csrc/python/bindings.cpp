@@ -94,7 +94,7 @@ StencilSpec make_spec(const std::string& kind, const std::string& dtype, double 
                       const std::vector<double>& w9 = kConv9Default) {
   StencilSpec s;
   s.coef.ref_precision = ref_precision;
-  life_rule_from_name(rule, s.coef.birth, s.coef.survive);
+  life_rule_from_name(rule, s.coef);
   s.kind = stencil_from_name(kind);
   s.dtype = dtype_from_name(dtype);
   s.coef.r = r;
@@ -443,12 +443,17 @@ PYBIND11_MODULE(_mdfx, m) {
     return hip_sweep_cost(make_spec(kind, dtype, -1, 0, 0, 0, 0, false, rule), nx, steps);
   }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("steps"), py::arg("rule") = "B3/S23");
   m.def("life_rule_parse", [](const std::string& text) {
-    uint32_t b = 0, s = 0;
-    life_rule_from_name(text, b, s);
-    return std::make_pair(b, s);
-  }, py::arg("text"), "(birth, survive) masks of a Life-like rule in B/S notation (life_rule_from_name)");
-  m.def("life_rule_format", &life_rule_name, py::arg("birth"), py::arg("survive"),
-        "the canonical B/S text of two 9-bit masks (life_rule_name)");
+    StencilCoef c;
+    life_rule_from_name(text, c);
+    return std::make_pair(c.birth, c.survive);
+  }, py::arg("text"), "(birth, survive) masks of a rule in B/S or B/S/C notation (life_rule_from_name)");
+  m.def("life_rule_states", [](const std::string& text) {
+    StencilCoef c;
+    life_rule_from_name(text, c);
+    return c.states;
+  }, py::arg("text"), "the number of cell states of a rule text: 2, or the C of a Generations rule B/S/C");
+  m.def("life_rule_format", &life_rule_name, py::arg("birth"), py::arg("survive"), py::arg("states") = 2,
+        "the canonical text of two 9-bit masks and a state count, /C<states> only above 2 (life_rule_name)");
   m.def("life_compat_init", [](int64_t h, int64_t w, double density, unsigned seed) {
     py::array_t<uint8_t> a({h, w});
     cpu_life_compat_init(a.mutable_data(), h, w, density, seed);

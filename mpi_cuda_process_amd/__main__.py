@@ -48,7 +48,8 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("--timeout", type=float, default=0.0)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--rule", default="B3/S23",
-                   help="life: any Life-like rule in B/S notation, e.g. B36/S23, B3678/S34678, B2/S")
+                   help="life: any Life-like rule in B/S notation, e.g. B36/S23, B3678/S34678, B2/S, or a "
+                        "Generations rule B/S/C with 2..256 cell states, e.g. B2/S345/C4")
     p.add_argument("--weights", default="", metavar="W,W,...",
                    help="star7: the seven weights c0,xm,xp,ym,yp,zm,zp (default 0.3,0.2,0.2,0.1,0.1,0.05,0.05); "
                         "conv9: the nine weights, row-major (default 0.06,0.10,0.02,0.14,0.36,0.14,0.02,0.10,0.06)")

@@ -7,7 +7,8 @@ the default initial condition. Families (reference parity in brackets):
   [MDF_kernel.cu:10-22 update, :88-99 initial grid]
 * :func:`life2d`  — Conway's Game of Life, Moore-8, B3/S23, dead frame, density 0.15
   [kernel.cu:10-68 update, :131-146 initial grid]; ``rule="B36/S23"`` runs any other Life-like
-  (outer-totalistic) rule
+  (outer-totalistic) rule, ``rule="B2/S345/C4"`` a Generations rule with C cell states (0 dead,
+  1 alive, 2 .. C-1 dying; Brian's Brain ``B2/S/C3``, Star Wars ``B2/S345/C4``)
 * :func:`heat3d`  — 3D 7-point heat / Jacobi (headline benchmark, BASELINE.json configs 2, 3, 5)
 * :func:`box27`   — 3D 27-point weighted stencil (BASELINE.json config 4)
 * :func:`box9`    — 2D 9-point weighted stencil (centre, edge and corner weights), Dirichlet edges
@@ -71,7 +72,9 @@ class Problem:
     # MDF_kernel.cu:20) instead of wholly in the field type; single-step sweeps only
     ref_precision: bool = False
     # Life only: the rule in B/S notation (digits = neighbour counts that give birth / let a cell
-    # survive), any of the 2^18 outer-totalistic Moore rules; parsed by the native core
+    # survive), any of the 2^18 outer-totalistic Moore rules, optionally with /C<n>: a Generations rule
+    # with n = 2 .. 256 cell states (``states``); parsed by the native core, and the text carries the
+    # state count through coef_kwargs() to every native call
     rule: str = "B3/S23"
     init: InitCondition = field(default_factory=InitCondition)
 
@@ -134,8 +137,13 @@ class Problem:
                     wzp=self.wzp, w9=self.w9)
 
     @property
+    def states(self) -> int:
+        """Cell states: 2, or the C of a Generations rule B/S/C."""
+        return native_states(self.rule) if self.kind == "life" else 2
+
+    @property
     def conway(self) -> bool:
-        return self.kind != "life" or native_rule(self.rule) == (0x008, 0x00C)
+        return self.kind != "life" or (native_rule(self.rule) == (0x008, 0x00C) and self.states == 2)
 
     def describe(self) -> str:
         shape = "%dx%d" % (self.nz, self.nx) if self.dims == 2 else "%dx%dx%d" % (self.nx, self.ny, self.nz)
@@ -149,6 +157,13 @@ def native_rule(rule: str) -> tuple:
     return tuple(native().life_rule_parse(rule))
 
 
+def native_states(rule: str) -> int:
+    """The number of cell states of a rule text (2 without a /C part), through the native parser."""
+    from .._native import native
+
+    return int(native().life_rule_states(rule))
+
+
 def mdf2d(h: int = 256, w: int = 256, dtype: str = "f32", r: float = 0.25,
           init: Optional[InitCondition] = None, ref_precision: bool = False) -> Problem:
     """2D 5-point MDF (finite-difference) heat / Jacobi problem, Dirichlet edges 100.
@@ -160,7 +175,9 @@ def mdf2d(h: int = 256, w: int = 256, dtype: str = "f32", r: float = 0.25,
 def life2d(h: int = 256, w: int = 256, density: float = 0.15, seed: int = 1,
            init: Optional[InitCondition] = None, rule: str = "B3/S23") -> Problem:
     """Game of Life on an h x w board with a dead frame: Conway's rule, or any Life-like ``rule``
-    (HighLife "B36/S23", Day & Night "B3678/S34678", Seeds "B2/S", ...)."""
+    (HighLife "B36/S23", Day & Night "B3678/S34678", Seeds "B2/S", ...), or a Generations rule
+    "B<n>/S<n>/C<states>" whose cells age through states 2 .. C-1 before they die (cells hold 0 .. C-1;
+    the ``life`` initial condition writes 0 and 1)."""
     return Problem("life", nx=w, ny=1, nz=h, dtype="u8", rule=rule,
                    init=init or InitCondition(kind="life", density=density, seed=seed))
 

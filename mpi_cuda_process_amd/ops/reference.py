@@ -112,26 +112,31 @@ def star13(u: torch.Tensor, c0: float = 0.25, c1: float = 2.0 / 15.0, c2: float 
 
 
 def life(u: torch.Tensor, rule: str = "B3/S23") -> torch.Tensor:
-    """Game of Life with a held (dead) frame, Conway's B3/S23 or any Life-like ``rule``; ``u`` is
-    (h, 1, w) or (h, w) uint8. Integer arithmetic: the neighbour count, then a lookup in the rule's
-    two 9-bit masks."""
-    from ..models import native_rule
+    """Game of Life with a held frame, Conway's B3/S23, any Life-like ``rule`` or a Generations rule
+    B/S/C with C cell states (0 dead, 1 alive, 2 .. C-1 dying); ``u`` is (h, 1, w) or (h, w) uint8.
+    Integer arithmetic: the count of neighbours in state 1, a lookup in the rule's two 9-bit masks, and
+    for the cells that advance (a live cell that does not survive, a dying cell) (s + 1) % C."""
+    from ..models import native_rule, native_states
 
     birth, survive = native_rule(rule)
+    states = native_states(rule)
     squeeze = u.dim() == 2
     g = (u if squeeze else u[:, 0, :]).to(torch.int32)
     out = g.clone()
     if min(g.shape) >= 3:
         h, w = g.shape
+        one = (g == 1).to(torch.int32)
         n = torch.zeros_like(g[1:-1, 1:-1])
         for dz in (-1, 0, 1):
             for dx in (-1, 0, 1):
                 if dz == 0 and dx == 0:
                     continue
-                n += g[1 + dz:h - 1 + dz, 1 + dx:w - 1 + dx]
-        alive = g[1:-1, 1:-1]
-        table = torch.where(alive == 1, torch.full_like(n, survive), torch.full_like(n, birth))
-        out[1:-1, 1:-1] = (table >> n) & 1
+                n += one[1 + dz:h - 1 + dz, 1 + dx:w - 1 + dx]
+        s = g[1:-1, 1:-1]
+        table = torch.where(s == 1, torch.full_like(n, survive), torch.full_like(n, birth))
+        stays = ((table >> n) & 1) == 1  # born, or survives
+        out[1:-1, 1:-1] = torch.where((s <= 1) & stays, torch.ones_like(s),
+                                      torch.where(s == 0, s, (s + 1) % states))
     out = out.to(torch.uint8)
     return out if squeeze else out.unsqueeze(1)
 
