@@ -78,6 +78,10 @@ bool hip_region_signals(const StencilSpec& spec, const FieldLayout& lay, int ste
 // >= C is the caller's error with an unspecified result (no fault). C = 3 .. 32 runs life_gen_bits at
 // steps 1, 2, 3, 4, 6, 8; C > 32 has the naive single step only, so this returns false for steps > 1.
 bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int steps);
+// The kernel family a one-region hip_stencil launch of `steps` steps runs on this layout ("heat7_wxk",
+// "box27_tb2", "life_rule_bits", ..., "naive"; for steps = 1 by the current kernel variant), "" where
+// hip_supports_steps is false.
+const char* hip_kernel_name(const StencilSpec& spec, const FieldLayout& lay, int steps);
 // The deepest fused sweep that is a measured win for this stencil at row width nx (before any
 // cap by slab depth): 8 for the 2D MDF, 12 for Life, 4 for the 3D 7-point where heat7_wxk's x
 // segments cover the row efficiently, else 2

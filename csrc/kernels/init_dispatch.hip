@@ -13,69 +13,12 @@
 #include <string>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "mdfx/kernels.hpp"
 
 namespace mdfx {
 namespace dev {
 
-void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* out, double* resid,
-                  hipStream_t s);
-template <class T>
-void launch_heat7(const Geo& g, const T* in, T* out, T r, double* resid, hipStream_t s);
-template <class T>
-void launch_jacobi5(const Geo& g, const T* in, T* out, T r, double* resid, hipStream_t s, bool ref);
-template <class T>
-void launch_jacobi5_tb2(const Geo& g, const T* in, T* out, T r, double* resid, hipStream_t s);
-template <class T>
-void launch_jacobi5_tbk(const Geo& g, const T* in, T* out, T r, int steps, double* resid, hipStream_t s,
-                        bool ref_precision);
-template <class T>
-void launch_box27_tb2(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
-template <class T>
-bool box27_tb2_supported(const Geo& g);
-template <class T>
-void launch_box27(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid,
-                  hipStream_t s);
-// 2D 9-point: box9_wave (steps = 1) and box9_tbk (2, 3, 4, 6, 8 fused steps), stencil_box9.hip
-template <class T>
-void launch_box9(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
-// 2D 9-point with nine weights: conv9_tbk (1, 2, 3, 4, 6, 8 steps per sweep), stencil_conv9.hip
-template <class T>
-void launch_conv9(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
-// 3D 7-point star with seven weights: star7_tbk (1, 2, 3, 4 steps per sweep), stencil_star7.hip
-template <class T>
-void launch_star7(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
-// 3D radius-2 star: star13_tbk (1, 2 steps per sweep), stencil_star13.hip
-template <class T>
-void launch_star13(const Geo& g, const T* in, T* out, const StencilCoef& c, int steps, double* resid, hipStream_t s);
-void launch_life(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
-void launch_life_tb2(const Geo& g, const uint8_t* in, uint8_t* out, double* resid, hipStream_t s);
-void launch_life_tbk(const Geo& g, const uint8_t* in, uint8_t* out, int steps, double* resid, hipStream_t s);
-// any rule but Conway's: life_rule_bits (1, 2, 3, 4, 6, 8, 12, 16 generations), stencil_life_rule.hip
-void launch_life_rule(const Geo& g, const uint8_t* in, uint8_t* out, uint32_t birth, uint32_t survive, int steps,
-                      double* resid, hipStream_t s);
-// a Generations rule with 3 .. 32 states: life_gen_bits (1, 2, 3, 4, 6, 8 generations), stencil_life_gen.hip
-void launch_life_gen(const Geo& g, const uint8_t* in, uint8_t* out, uint32_t birth, uint32_t survive, int states,
-                     int steps, double* resid, hipStream_t s);
-bool life_gen_supported(int states, int steps);
-template <class T>
-void launch_heat7_tb2(const Geo& g, const T* in, T* out, T r, double* resid, hipStream_t s);
-template <class T>
-bool heat7_tb2_supported(const Geo& g);
-template <class T>
-void launch_heat7_tbk(const Geo& g, const T* in, T* out, T r, int steps, double* resid, hipStream_t s);
-template <class T>
-bool heat7_tbk_supported(const Geo& g, int steps);
-template <class T>
-void launch_heat7_wtk(const Geo& g, const T* in, T* out, T r, int steps, double* resid, hipStream_t s);
-bool heat7_wtk_supported(int steps);
-bool heat7_wxk_supported(int steps);
-template <class T>
-void launch_heat7_wxk(const Geo& g, const T* in, T* out, T r, int steps, double* resid, hipStream_t s);
-template <class T>
-void launch_box27_wxk(const Geo& g, const T* in, T* out, const StencilCoef& cf, int steps, double* resid,
-                      hipStream_t s);
-double heat7_wtk_xeff(int64_t nx, int esize, int steps);
 // 3D 7-point sweeps of K >= 3 steps run heat7_wtk (wave-independent tiles; 1024^3 fp32 K = 3:
 // 1443 vs 1081 GCells/s for heat7_tbk, profiles/archive/r02_wtk/README.txt; heat7_tbk's K = 3 / 4 were
 // removed in round 5)
@@ -202,6 +145,103 @@ static Geo make_geo(const FieldLayout& lay, int64_t lz_begin, int64_t lz_end) {
 static std::mutex g_variant_mu;
 static std::string g_variant = "auto";
 
+// The launcher families of launchers.hpp; None: no kernel serves the request.
+enum class Kernel {
+  None, Naive, Heat7Zw, Heat7Tb2, Heat7Tbk, Heat7Wtk, Heat7Wxk, Box27Zw, Box27Tb2, Box27Wxk, Jacobi5Wave, Jacobi5Tb2,
+  Jacobi5Tbk, Box9, Conv9, Star7, Star13, LifeWave, LifeTb2, LifeTbk, LifeRule, LifeGen
+};
+
+static const char* kernel_name(Kernel k) {
+  static const char* const names[] = {
+      "", "naive", "heat7_zw", "heat7_tb2", "heat7_tbk", "heat7_wtk", "heat7_wxk", "box27_zw", "box27_tb2", "box27_wxk",
+      "jacobi5_wave", "jacobi5_tb2", "jacobi5_tbk", "box9_tbk", "conv9_tbk", "star7_tbk", "star13_tbk", "life_wave",
+      "life_tb2", "life_bits", "life_rule_bits", "life_gen_bits"};
+  static_assert(sizeof(names) / sizeof(*names) == (size_t)Kernel::LifeGen + 1, "one name per Kernel, in its order");
+  return names[(int)k];
+}
+
+struct Choice {
+  Kernel kernel;  // what a one-region launch runs
+  bool pair;      // two regions go out as one launch (else one after the other)
+  bool signals;   // the kernel honours RegionArgs::sig
+};
+
+// Which kernel serves (stencil, dtype, layout, steps): the one place that decides it. hip_supports_steps,
+// hip_region_signals, hip_kernel_name and the launch in hip_stencil all read this answer.
+static Choice choose(const StencilSpec& spec, const FieldLayout& lay, int steps) {
+  const auto one = [](Kernel k) { return Choice{k, false, false}; };
+  if (steps == 1) {
+    // pencil layouts: single steps through the one-cell-per-lane kernels (every stencil); the tuned
+    // kernels but heat7_wxk assume slab geometry
+    bool naive = lay.pencil();
+    if (!naive) {
+      std::lock_guard<std::mutex> lk(g_variant_mu);
+      naive = g_variant == "naive";
+    }
+    if (naive) return one(Kernel::Naive);
+    switch (spec.kind) {
+      case StencilKind::Heat7: return one(Kernel::Heat7Zw);
+      case StencilKind::Jacobi5: return one(Kernel::Jacobi5Wave);
+      case StencilKind::Box27: return one(Kernel::Box27Zw);
+      case StencilKind::Box9: return one(Kernel::Box9);
+      case StencilKind::Conv9: return one(Kernel::Conv9);
+      case StencilKind::Star7: return one(Kernel::Star7);
+      case StencilKind::Star13: return one(Kernel::Star13);
+      case StencilKind::Life:
+        // a Generations rule of more than 32 states has the naive single step only
+        if (spec.generations()) return one(life_gen_supported(spec.coef.states, 1) ? Kernel::LifeGen : Kernel::Naive);
+        return one(spec.conway() ? Kernel::LifeWave : Kernel::LifeRule);
+    }
+    return one(Kernel::None);
+  }
+  if (steps < 2 || lay.halo < stencil_radius(spec.kind) * steps) return one(Kernel::None);
+  if (lay.pencil()) {
+    // pencils (y ghost rows): the fused 7-point sweep of heat7_wxk only; two regions go out as one
+    // launch where a slab of these rows would run heat7_wxk too
+    if (spec.kind == StencilKind::Heat7 && heat7_wxk_supported(steps) && lay.hy >= steps && knobs().h7_wxk != 0)
+      return {Kernel::Heat7Wxk, use_wxk(spec.dtype, lay.global.nx, steps), false};
+    return one(Kernel::None);
+  }
+  const bool k2d = steps == 2 || steps == 3 || steps == 4 || steps == 6 || steps == 8;
+  switch (spec.kind) {
+    case StencilKind::Jacobi5:  // deep temporal blocking of the 2D problems
+      if (!((spec.dtype == DType::F32 || spec.dtype == DType::F64) && k2d)) return one(Kernel::None);
+      // ref_precision takes the mixed kernels (jacobi5_tbk REF) only where it can change a bit (mixed_update())
+      return one(steps > 2 || spec.mixed_update() ? Kernel::Jacobi5Tbk : Kernel::Jacobi5Tb2);
+    case StencilKind::Box9: return one(k2d ? Kernel::Box9 : Kernel::None);
+    case StencilKind::Conv9: return one(k2d ? Kernel::Conv9 : Kernel::None);
+    case StencilKind::Star7: return one(steps <= 4 ? Kernel::Star7 : Kernel::None);    // any nx, ny, nz
+    case StencilKind::Star13: return one(steps == 2 ? Kernel::Star13 : Kernel::None);  // any nx, ny, nz
+    case StencilKind::Life:
+      // a Generations rule: life_gen_bits' depths for 3 .. 32 states; more states have the naive single step only
+      if (spec.generations()) return one(life_gen_supported(spec.coef.states, steps) ? Kernel::LifeGen : Kernel::None);
+      // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
+      if (!(k2d || steps == 12 || steps == 16)) return one(Kernel::None);
+      if (!spec.conway()) return one(Kernel::LifeRule);
+      return one(steps > 2 ? Kernel::LifeTbk : Kernel::LifeTb2);
+    case StencilKind::Box27: {
+      if (steps == 3) return {Kernel::Box27Wxk, true, false};  // (any row width)
+      bool tb2 = false;
+      const Geo g = make_geo(lay, lay.halo, lay.halo + lay.nzl());
+      MDFX_BY_DTYPE(spec.dtype, nullptr, nullptr, tb2 = steps == 2 && box27_tb2_supported<T>(g));
+      return one(tb2 ? Kernel::Box27Tb2 : Kernel::None);
+    }
+    case StencilKind::Heat7: {
+      if (use_wtk(steps, spec.dtype)) {
+        if (use_wxk(spec.dtype, lay.global.nx, steps)) return {Kernel::Heat7Wxk, true, true};
+        return one(Kernel::Heat7Wtk);  // (fp64 only: use_wxk holds for every fp32 sweep)
+      }
+      // rows within one block: the streaming K-step kernel; wider rows (K = 2): heat7_tb2 x tiles
+      bool tbk = false, tb2 = false;
+      const Geo g = make_geo(lay, lay.halo, lay.halo + lay.nzl());
+      MDFX_BY_DTYPE(spec.dtype, nullptr, nullptr, tbk = heat7_tbk_supported<T>(g, steps);
+                    tb2 = steps == 2 && heat7_tb2_supported<T>(g));
+      return one(tbk ? Kernel::Heat7Tbk : tb2 ? Kernel::Heat7Tb2 : Kernel::None);
+    }
+  }
+  return one(Kernel::None);
+}
+
 }  // namespace dev
 
 int64_t hip_device_check_violations() {
@@ -265,43 +305,15 @@ void hip_init(const InitSpec& init, const FieldLayout& lay, void* buf, void* str
 }
 
 bool hip_supports_steps(const StencilSpec& spec, const FieldLayout& lay, int steps) {
-  if (steps == 1) return true;
-  if (steps < 2 || lay.halo < stencil_radius(spec.kind) * steps) return false;
-  if (lay.pencil())  // pencils (y ghost rows): the fused 7-point sweep of heat7_wxk only
-    return spec.kind == StencilKind::Heat7 && dev::heat7_wxk_supported(steps) && lay.hy >= steps &&
-           dev::knobs().h7_wxk != 0;
-  const bool k2d = steps == 2 || steps == 3 || steps == 4 || steps == 6 || steps == 8;
-  if (spec.kind == StencilKind::Jacobi5)  // deep temporal blocking of the 2D problems
-    return (spec.dtype == DType::F32 || spec.dtype == DType::F64) && k2d;  // ref precision too (jacobi5_tbk REF)
-  if (spec.kind == StencilKind::Box9) return k2d;  // box9_tbk
-  if (spec.kind == StencilKind::Conv9) return k2d;  // conv9_tbk
-  if (spec.kind == StencilKind::Star7) return steps <= 4;  // star7_tbk: any nx, ny, nz
-  if (spec.kind == StencilKind::Star13) return steps == 2;  // star13_tbk: any nx, ny, nz
-  // a Generations rule: life_gen_bits' depths for 3 .. 32 states; more states have the naive single step only
-  if (spec.kind == StencilKind::Life && spec.generations()) return dev::life_gen_supported(spec.coef.states, steps);
-  // 12 / 16: life_bits; the same depths for every other rule through life_rule_bits
-  if (spec.kind == StencilKind::Life) return k2d || steps == 12 || steps == 16;
-  if (spec.kind == StencilKind::Heat7 && steps > 2) {  // deep temporal blocking (rows within one block)
-    if (dev::use_wtk(steps, spec.dtype)) return true;
-    const dev::Geo g = dev::make_geo(lay, lay.halo, lay.halo + lay.nzl());
-    return spec.dtype == DType::F32 ? dev::heat7_tbk_supported<float>(g, steps)
-                                    : dev::heat7_tbk_supported<double>(g, steps);
-  }
-  if (spec.kind == StencilKind::Box27 && steps == 3) return true;  // box27_wxk (any row width)
-  if (steps != 2) return false;
-  if (spec.kind == StencilKind::Box27) {
-    const dev::Geo g = dev::make_geo(lay, lay.halo, lay.halo + lay.nzl());
-    return spec.dtype == DType::F32 ? dev::box27_tb2_supported<float>(g) : dev::box27_tb2_supported<double>(g);
-  }
-  if (spec.kind != StencilKind::Heat7) return false;
-  const dev::Geo g = dev::make_geo(lay, lay.halo, lay.halo + lay.nzl());
-  return spec.dtype == DType::F32 ? dev::heat7_tb2_supported<float>(g) : dev::heat7_tb2_supported<double>(g);
+  return dev::choose(spec, lay, steps).kernel != dev::Kernel::None;
 }
 
 bool hip_region_signals(const StencilSpec& spec, const FieldLayout& lay, int steps) {
-  return !lay.pencil() && spec.kind == StencilKind::Heat7 &&
-         (steps == 3 || steps == 4 || steps == 5) && lay.halo >= steps &&
-         dev::use_wtk(steps, spec.dtype) && dev::use_wxk(spec.dtype, lay.global.nx, steps);
+  return dev::choose(spec, lay, steps).signals;
+}
+
+const char* hip_kernel_name(const StencilSpec& spec, const FieldLayout& lay, int steps) {
+  return dev::kernel_name(dev::choose(spec, lay, steps).kernel);
 }
 
 // Generations rules (life_gen_bits, 3 .. 32 states in P = 2 .. 5 bit planes). 32768^2, density 0.5, GCells/s
@@ -455,14 +467,11 @@ double hip_sweep_cost(const StencilSpec& spec, int64_t nx, int steps) {
 }
 
 void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
+  const dev::Choice c = dev::choose(spec, a.lay, a.steps);
   if (a.lz2_end > a.lz2_begin) {
-    // two regions in one call: heat7_wtk sweeps them in ONE launch (both boundary regions of a
-    // slab: one fill of the device, one launch gap); every other kernel runs them one after the other
-    const bool fuse = a.lz_end > a.lz_begin &&
-                      ((a.steps > 1 && spec.kind == StencilKind::Heat7 && dev::use_wtk(a.steps, spec.dtype) &&
-                        dev::use_wxk(spec.dtype, a.lay.global.nx, a.steps)) ||
-                       (spec.kind == StencilKind::Box27 && a.steps == 3));
-    if (!fuse) {
+    // two regions in one call: heat7_wxk and box27_wxk sweep them in ONE launch (both boundary regions
+    // of a slab: one fill of the device, one launch gap); every other kernel runs them one after the other
+    if (!(c.pair && a.lz_end > a.lz_begin)) {
       RegionArgs r1 = a, r2 = a;
       r1.lz2_begin = r1.lz2_end = r2.lz2_begin = r2.lz2_end = 0;
       r2.lz_begin = a.lz2_begin;
@@ -487,7 +496,7 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
   g.lz2_end = a.lz2_end;
   g.min_rounds = std::max(1, std::min(4, a.min_rounds));
   if (a.sig) {
-    MDFX_CHECK(hip_region_signals(spec, a.lay, a.steps) && a.lz2_end <= a.lz2_begin && a.sig_z > a.lz_begin &&
+    MDFX_CHECK(c.signals && a.lz2_end <= a.lz2_begin && a.sig_z > a.lz_begin &&
                    a.sig_z <= a.lz_end,
                "a folded boundary (RegionArgs::sig) needs a one-region slab sweep through heat7_wxk");
     g.sig = a.sig;
@@ -499,175 +508,55 @@ void hip_stencil(const StencilSpec& spec, const RegionArgs& a, void* stream) {
     g.ly_begin = a.ly_begin;
     g.ly_end = a.ly_end;
   }
+  MDFX_CHECK(c.kernel != dev::Kernel::None,
+             a.lay.pencil()
+                 ? format("no fused %d-step kernel for %s %s on a pencil layout (heat7_wxk: the 3D 7-point, K = 3 / 4)",
+                          a.steps, stencil_name(spec.kind), dtype_name(spec.dtype))
+                 : format("no fused %d-step kernel for %s %s at nx=%lld (halo %d)", a.steps, stencil_name(spec.kind),
+                          dtype_name(spec.dtype), (long long)a.lay.global.nx, a.lay.halo));
   hipStream_t s = (hipStream_t)stream;
-  if (a.lay.pencil()) {
-    // pencil layouts: the fused 7-point sweeps through heat7_wxk, single steps through the
-    // one-cell-per-lane kernels (every stencil); the other tuned kernels assume slab geometry
-    if (a.steps != 1) {
-      MDFX_CHECK(hip_supports_steps(spec, a.lay, a.steps),
-                 format("no fused %d-step kernel for %s %s on a pencil layout (heat7_wxk: the 3D 7-point, K = 3 / 4)",
-                        a.steps, stencil_name(spec.kind), dtype_name(spec.dtype)));
-      if (spec.dtype == DType::F32)
-        dev::launch_heat7_wxk<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.steps, a.resid, s);
-      else
-        dev::launch_heat7_wxk<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.steps, a.resid, s);
-    } else {
-      MDFX_CHECK(a.lz2_end <= a.lz2_begin, "single pencil steps take one region per call");
-      dev::naive_launch(spec, g, a.in, a.out, a.resid, s);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) MDFX_FAIL(std::string("stencil launch failed: ") + hipGetErrorString(e));
-    return;
-  }
-  if (a.steps != 1) {
-    MDFX_CHECK(hip_supports_steps(spec, a.lay, a.steps),
-               format("no fused %d-step kernel for %s %s at nx=%lld (halo %d)", a.steps, stencil_name(spec.kind),
-                      dtype_name(spec.dtype), (long long)a.lay.global.nx, a.lay.halo));
-    if (spec.kind == StencilKind::Box27 && a.steps == 3) {
-      if (spec.dtype == DType::F32)
-        dev::launch_box27_wxk<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 3, a.resid, s);
-      else
-        dev::launch_box27_wxk<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 3, a.resid, s);
-    } else if (spec.kind == StencilKind::Box27) {
-      if (spec.dtype == DType::F32)
-        dev::launch_box27_tb2<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.resid, s);
-      else
-        dev::launch_box27_tb2<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.resid, s);
-    } else if (spec.kind == StencilKind::Box9) {
-      if (spec.dtype == DType::F32)
-        dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
-      else
-        dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
-    } else if (spec.kind == StencilKind::Conv9) {
-      if (spec.dtype == DType::F32)
-        dev::launch_conv9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
-      else
-        dev::launch_conv9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
-    } else if (spec.kind == StencilKind::Star7) {
-      if (spec.dtype == DType::F32)
-        dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
-      else
-        dev::launch_star7<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
-    } else if (spec.kind == StencilKind::Star13) {
-      if (spec.dtype == DType::F32)
-        dev::launch_star13<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.steps, a.resid, s);
-      else
-        dev::launch_star13<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.steps, a.resid, s);
-    } else if (spec.kind == StencilKind::Life && spec.generations()) {
-      dev::launch_life_gen(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive,
-                           spec.coef.states, a.steps, a.resid, s);
-    } else if (spec.kind == StencilKind::Life && !spec.conway()) {
-      dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, a.steps,
-                            a.resid, s);
-    } else if (spec.kind == StencilKind::Life) {
-      if (a.steps > 2)
-        dev::launch_life_tbk(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.steps, a.resid, s);
-      else
-        dev::launch_life_tb2(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.resid, s);
-    } else if (spec.kind == StencilKind::Jacobi5) {
-      // ref_precision takes the mixed kernels only where it can change a bit (mixed_update())
-      const bool mixed = spec.mixed_update();
-      if (a.steps > 2 || mixed) {
-        if (spec.dtype == DType::F32)
-          dev::launch_jacobi5_tbk<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.steps, a.resid, s,
-                                         mixed);
-        else
-          dev::launch_jacobi5_tbk<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.steps, a.resid, s,
-                                          false);
-      } else if (spec.dtype == DType::F32) {
-        dev::launch_jacobi5_tb2<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.resid, s);
-      } else {
-        dev::launch_jacobi5_tb2<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.resid, s);
-      }
-    } else if (dev::use_wtk(a.steps, spec.dtype) && dev::use_wxk(spec.dtype, a.lay.global.nx, a.steps)) {
-      if (spec.dtype == DType::F32)
-        dev::launch_heat7_wxk<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.steps, a.resid, s);
-      else
-        dev::launch_heat7_wxk<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.steps, a.resid, s);
-    } else if (dev::use_wtk(a.steps, spec.dtype)) {  // (fp64 only: use_wxk holds for every fp32 sweep)
+  const StencilCoef& cf = spec.coef;
+  const uint8_t* const u8in = (const uint8_t*)a.in;
+  uint8_t* const u8out = (uint8_t*)a.out;
+  // (T, tin, tout: the field type and the typed a.in / a.out)
+#define MDFX_LAUNCH(...) MDFX_BY_DTYPE(spec.dtype, a.in, a.out, dev::__VA_ARGS__)
+  switch (c.kernel) {
+    case dev::Kernel::None: break;
+    case dev::Kernel::Naive: dev::naive_launch(spec, g, a.in, a.out, a.resid, s); break;
+    case dev::Kernel::Heat7Zw: MDFX_LAUNCH(launch_heat7<T>(g, tin, tout, (T)spec.rate(), a.resid, s)); break;
+    case dev::Kernel::Heat7Tb2: MDFX_LAUNCH(launch_heat7_tb2<T>(g, tin, tout, (T)spec.rate(), a.resid, s)); break;
+    case dev::Kernel::Heat7Tbk:
+      MDFX_LAUNCH(launch_heat7_tbk<T>(g, tin, tout, (T)spec.rate(), a.steps, a.resid, s));
+      break;
+    case dev::Kernel::Heat7Wtk:
       dev::launch_heat7_wtk<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.steps, a.resid, s);
-    } else if (a.steps > 2 || (spec.dtype == DType::F32 ? dev::heat7_tbk_supported<float>(g, 2)
-                                                        : dev::heat7_tbk_supported<double>(g, 2))) {
-      // rows within one block: the streaming K-step kernel; wider rows (K = 2): heat7_tb2 x tiles
-      if (spec.dtype == DType::F32)
-        dev::launch_heat7_tbk<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.steps, a.resid, s);
-      else
-        dev::launch_heat7_tbk<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.steps, a.resid, s);
-    } else if (spec.dtype == DType::F32) {
-      dev::launch_heat7_tb2<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.resid, s);
-    } else {
-      dev::launch_heat7_tb2<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.resid, s);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) MDFX_FAIL(std::string("stencil launch failed: ") + hipGetErrorString(e));
-    return;
+      break;
+    case dev::Kernel::Heat7Wxk:
+      MDFX_LAUNCH(launch_heat7_wxk<T>(g, tin, tout, (T)spec.rate(), a.steps, a.resid, s));
+      break;
+    case dev::Kernel::Box27Zw: MDFX_LAUNCH(launch_box27<T>(g, tin, tout, cf, a.resid, s)); break;
+    case dev::Kernel::Box27Tb2: MDFX_LAUNCH(launch_box27_tb2<T>(g, tin, tout, cf, a.resid, s)); break;
+    case dev::Kernel::Box27Wxk: MDFX_LAUNCH(launch_box27_wxk<T>(g, tin, tout, cf, a.steps, a.resid, s)); break;
+    case dev::Kernel::Jacobi5Wave:
+      MDFX_LAUNCH(launch_jacobi5<T>(g, tin, tout, (T)spec.rate(), a.resid, s, spec.mixed_update()));
+      break;
+    case dev::Kernel::Jacobi5Tb2: MDFX_LAUNCH(launch_jacobi5_tb2<T>(g, tin, tout, (T)spec.rate(), a.resid, s)); break;
+    case dev::Kernel::Jacobi5Tbk:
+      MDFX_LAUNCH(launch_jacobi5_tbk<T>(g, tin, tout, (T)spec.rate(), a.steps, a.resid, s, spec.mixed_update()));
+      break;
+    case dev::Kernel::Box9: MDFX_LAUNCH(launch_box9<T>(g, tin, tout, cf, a.steps, a.resid, s)); break;
+    case dev::Kernel::Conv9: MDFX_LAUNCH(launch_conv9<T>(g, tin, tout, cf, a.steps, a.resid, s)); break;
+    case dev::Kernel::Star7: MDFX_LAUNCH(launch_star7<T>(g, tin, tout, cf, a.steps, a.resid, s)); break;
+    case dev::Kernel::Star13: MDFX_LAUNCH(launch_star13<T>(g, tin, tout, cf, a.steps, a.resid, s)); break;
+    case dev::Kernel::LifeWave: dev::launch_life(g, u8in, u8out, a.resid, s); break;
+    case dev::Kernel::LifeTb2: dev::launch_life_tb2(g, u8in, u8out, a.resid, s); break;
+    case dev::Kernel::LifeTbk: dev::launch_life_tbk(g, u8in, u8out, a.steps, a.resid, s); break;
+    case dev::Kernel::LifeRule: dev::launch_life_rule(g, u8in, u8out, cf.birth, cf.survive, a.steps, a.resid, s); break;
+    case dev::Kernel::LifeGen:
+      dev::launch_life_gen(g, u8in, u8out, cf.birth, cf.survive, cf.states, a.steps, a.resid, s);
+      break;
   }
-  std::string variant;
-  {
-    std::lock_guard<std::mutex> lk(dev::g_variant_mu);
-    variant = dev::g_variant;
-  }
-  if (variant == "naive") {
-    dev::naive_launch(spec, g, a.in, a.out, a.resid, s);
-  } else {
-    switch (spec.kind) {
-      case StencilKind::Heat7:
-        if (spec.dtype == DType::F32)
-          dev::launch_heat7<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.resid, s);
-        else
-          dev::launch_heat7<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.resid, s);
-        break;
-      case StencilKind::Jacobi5:
-        if (spec.dtype == DType::F32)
-          dev::launch_jacobi5<float>(g, (const float*)a.in, (float*)a.out, (float)spec.rate(), a.resid, s,
-                                     spec.mixed_update());
-        else
-          dev::launch_jacobi5<double>(g, (const double*)a.in, (double*)a.out, spec.rate(), a.resid, s, false);
-        break;
-      case StencilKind::Box27:
-        if (spec.dtype == DType::F32)
-          dev::launch_box27<float>(g, (const float*)a.in, (float*)a.out, spec.coef, a.resid, s);
-        else
-          dev::launch_box27<double>(g, (const double*)a.in, (double*)a.out, spec.coef, a.resid, s);
-        break;
-      case StencilKind::Box9:
-        if (spec.dtype == DType::F32)
-          dev::launch_box9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
-        else
-          dev::launch_box9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
-        break;
-      case StencilKind::Conv9:
-        if (spec.dtype == DType::F32)
-          dev::launch_conv9<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
-        else
-          dev::launch_conv9<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
-        break;
-      case StencilKind::Star7:
-        if (spec.dtype == DType::F32)
-          dev::launch_star7<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
-        else
-          dev::launch_star7<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
-        break;
-      case StencilKind::Star13:
-        if (spec.dtype == DType::F32)
-          dev::launch_star13<float>(g, (const float*)a.in, (float*)a.out, spec.coef, 1, a.resid, s);
-        else
-          dev::launch_star13<double>(g, (const double*)a.in, (double*)a.out, spec.coef, 1, a.resid, s);
-        break;
-      case StencilKind::Life:
-        if (spec.generations() && dev::life_gen_supported(spec.coef.states, 1))
-          dev::launch_life_gen(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive,
-                               spec.coef.states, 1, a.resid, s);
-        else if (spec.generations())  // more than 32 states
-          dev::naive_launch(spec, g, a.in, a.out, a.resid, s);
-        else if (spec.conway())
-          dev::launch_life(g, (const uint8_t*)a.in, (uint8_t*)a.out, a.resid, s);
-        else
-          dev::launch_life_rule(g, (const uint8_t*)a.in, (uint8_t*)a.out, spec.coef.birth, spec.coef.survive, 1,
-                                a.resid, s);
-        break;
-    }
-  }
+#undef MDFX_LAUNCH
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) MDFX_FAIL(std::string("stencil launch failed: ") + hipGetErrorString(e));
 }

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "rowops.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
@@ -19,7 +20,6 @@
 namespace mdfx {
 namespace dev {
 
-int pick_zc(int64_t planes, int64_t columns, int zc_max, int blocks_target);
 int64_t resident_blocks(const void* kfn);
 int tbk_zc(int64_t planes, int64_t tiles, int64_t resident, int K, int min_rounds);
 

@@ -47,13 +47,12 @@
 #include <type_traits>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
 
 namespace mdfx {
 namespace dev {
-
-int pick_zc(int64_t planes, int64_t columns, int zc_max, int blocks_target);
 
 // one lane's 16-B slice of a row
 template <class T>

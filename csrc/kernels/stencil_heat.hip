@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
 

@@ -28,14 +28,13 @@
 #include <mutex>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "rowops.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
 
 namespace mdfx {
 namespace dev {
-
-int pick_zc(int64_t planes, int64_t columns, int zc_max, int blocks_target);
 
 template <class V, class T>
 __device__ __forceinline__ V vsplat_tb(T v) {

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "rowops.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"

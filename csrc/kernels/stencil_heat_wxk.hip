@@ -47,6 +47,7 @@
 #include <type_traits>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "rowops.hpp"
 #include "wxk_common.hpp"
 #include "mdfx/kernels.hpp"

@@ -10,14 +10,13 @@
 #include <algorithm>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "life_pack.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
 
 namespace mdfx {
 namespace dev {
-
-int pick_zc(int64_t planes, int64_t columns, int zc_max, int blocks_target);
 
 struct U2 {
   uint64_t lo, hi;

@@ -69,12 +69,11 @@
 #include <type_traits>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "mdfx/kernels.hpp"
 
 namespace mdfx {
 namespace dev {
-
-int pick_zc(int64_t planes, int64_t columns, int zc_max, int blocks_target);
 
 namespace {
 

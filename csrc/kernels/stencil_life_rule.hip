@@ -71,13 +71,12 @@
 #include <algorithm>
 
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "life_pack.hpp"
 #include "mdfx/kernels.hpp"
 
 namespace mdfx {
 namespace dev {
-
-int pick_zc(int64_t planes, int64_t columns, int zc_max, int blocks_target);
 
 namespace {
 

@@ -6,6 +6,7 @@
 // compute per thread, minus their defects: 64-bit grid-stride indexing (no __mul24, no floored
 // grid — SURVEY D10, D16) and explicit boundary handling (D8, D9).
 #include "kcommon.hpp"
+#include "launchers.hpp"
 #include "mdfx/kernels.hpp"
 #include "mdfx/stencil_math.hpp"
 
@@ -180,13 +181,6 @@ __global__ __launch_bounds__(256) void naive_life(const uint8_t* __restrict__ in
   if (RES) wave_atomic_add(resid, acc);
 }
 
-template <class T>
-void launch_box9_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
-template <class T>
-void launch_star7_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
-template <class T>
-void launch_star13_naive(const Geo& g, const T* in, T* out, const StencilCoef& c, double* resid, hipStream_t s);
-
 static int naive_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (int)std::min<int64_t>(std::max<int64_t>(b, 1), 256 * 32);
@@ -198,62 +192,37 @@ void naive_launch(const StencilSpec& spec, const Geo& g, const void* in, void* o
   if (n <= 0) return;
   const dim3 grd(naive_grid(n)), blk(256);
   const bool res = resid != nullptr;
-#define MDFX_NAIVE(KERNEL, T, ...)                                                              \
-  do {                                                                                          \
-    if (res)                                                                                    \
-      hipLaunchKernelGGL((KERNEL<T, true>), grd, blk, 0, s, (const T*)in, (T*)out, g, __VA_ARGS__, resid); \
-    else                                                                                        \
-      hipLaunchKernelGGL((KERNEL<T, false>), grd, blk, 0, s, (const T*)in, (T*)out, g, __VA_ARGS__, resid); \
+// (inside MDFX_BY_DTYPE: T, tin, tout)
+#define MDFX_NAIVE(KERNEL, ...)                                                               \
+  do {                                                                                        \
+    if (res)                                                                                  \
+      hipLaunchKernelGGL((KERNEL<T, true>), grd, blk, 0, s, tin, tout, g, __VA_ARGS__, resid);  \
+    else                                                                                      \
+      hipLaunchKernelGGL((KERNEL<T, false>), grd, blk, 0, s, tin, tout, g, __VA_ARGS__, resid); \
   } while (0)
+  const auto& c = spec.coef;
   switch (spec.kind) {
     case StencilKind::Heat7:
-      if (spec.dtype == DType::F32)
-        MDFX_NAIVE(naive_heat7, float, (float)spec.rate());
-      else
-        MDFX_NAIVE(naive_heat7, double, spec.rate());
+      MDFX_BY_DTYPE(spec.dtype, in, out, MDFX_NAIVE(naive_heat7, (T)spec.rate()));
       break;
     case StencilKind::Jacobi5:
-      if (spec.dtype == DType::F32)
-        MDFX_NAIVE(naive_jacobi5, float, (float)spec.rate(), (int)spec.coef.ref_precision);
-      else
-        MDFX_NAIVE(naive_jacobi5, double, spec.rate(), (int)spec.coef.ref_precision);
+      MDFX_BY_DTYPE(spec.dtype, in, out, MDFX_NAIVE(naive_jacobi5, (T)spec.rate(), (int)c.ref_precision));
       break;
-    case StencilKind::Box27: {
-      const auto& c = spec.coef;
-      if (spec.dtype == DType::F32)
-        MDFX_NAIVE(naive_box27, float, (float)c.c0, (float)c.c1, (float)c.c2, (float)c.c3);
-      else
-        MDFX_NAIVE(naive_box27, double, c.c0, c.c1, c.c2, c.c3);
+    case StencilKind::Box27:
+      MDFX_BY_DTYPE(spec.dtype, in, out, MDFX_NAIVE(naive_box27, (T)c.c0, (T)c.c1, (T)c.c2, (T)c.c3));
       break;
-    }
     case StencilKind::Box9:  // (the kernel lives in stencil_box9.hip, built without packed fp32 ops)
-      if (spec.dtype == DType::F32)
-        launch_box9_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
-      else
-        launch_box9_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
+      MDFX_BY_DTYPE(spec.dtype, in, out, launch_box9_naive<T>(g, tin, tout, c, resid, s));
       break;
     case StencilKind::Star7:  // (the kernel lives in stencil_star7.hip, built without packed fp32 ops)
-      if (spec.dtype == DType::F32)
-        launch_star7_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
-      else
-        launch_star7_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
+      MDFX_BY_DTYPE(spec.dtype, in, out, launch_star7_naive<T>(g, tin, tout, c, resid, s));
       break;
     case StencilKind::Conv9:
-      if (spec.dtype == DType::F32) {
-        sm::Conv9W<float> k;
-        for (int i = 0; i < 9; ++i) k.w[i] = (float)spec.coef.w9[i];
-        MDFX_NAIVE(naive_conv9, float, k);
-      } else {
-        sm::Conv9W<double> k;
-        for (int i = 0; i < 9; ++i) k.w[i] = spec.coef.w9[i];
-        MDFX_NAIVE(naive_conv9, double, k);
-      }
+      MDFX_BY_DTYPE(spec.dtype, in, out, sm::Conv9W<T> k; for (int i = 0; i < 9; ++i) k.w[i] = (T)c.w9[i];
+                    MDFX_NAIVE(naive_conv9, k));
       break;
     case StencilKind::Star13:  // (stencil_star13.hip, for the same reason)
-      if (spec.dtype == DType::F32)
-        launch_star13_naive<float>(g, (const float*)in, (float*)out, spec.coef, resid, s);
-      else
-        launch_star13_naive<double>(g, (const double*)in, (double*)out, spec.coef, resid, s);
+      MDFX_BY_DTYPE(spec.dtype, in, out, launch_star13_naive<T>(g, tin, tout, c, resid, s));
       break;
     case StencilKind::Life: {
       const TableRule tr{spec.coef.birth, spec.coef.survive};

@@ -405,6 +405,14 @@ PYBIND11_MODULE(_mdfx, m) {
     return hip_supports_steps(s, FieldLayout::make(Extent3{nx, ny, nz}, 0, nz, halo, dtype_from_name(dtype)), steps);
   }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("halo"),
      py::arg("steps"), py::arg("ref_precision") = false, py::arg("rule") = "B3/S23");
+  // (r: hip_supports_steps' arguments plus the 5-point rate, which decides jacobi5's mixed-precision kernel)
+  m.def("hip_kernel_name", [](const std::string& kind, const std::string& dtype, int64_t nx, int64_t ny,
+                              int64_t nz, int halo, int steps, bool ref_precision, const std::string& rule, double r) {
+    StencilSpec s = make_spec(kind, dtype, r, 0, 0, 0, 0, ref_precision, rule);
+    return std::string(
+        hip_kernel_name(s, FieldLayout::make(Extent3{nx, ny, nz}, 0, nz, halo, dtype_from_name(dtype)), steps));
+  }, py::arg("kind"), py::arg("dtype"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("halo"),
+     py::arg("steps"), py::arg("ref_precision") = false, py::arg("rule") = "B3/S23", py::arg("r") = -1.0);
   m.def("hip_fused_depth", [](const std::string& kind, const std::string& dtype, int64_t nx, bool ref_precision,
                               const std::string& rule) {
     StencilSpec s = make_spec(kind, dtype, -1, 0, 0, 0, 0, ref_precision, rule);
